@@ -13,13 +13,23 @@ One step = one pass of the hot path over one batch resident in HBM on every GPU:
   --config c1   one 64 KiB PUT message on the CPU (BASELINE configs[0]): µs per message for the
                 product host path and for the oracle; not the headline metric.
 
-Prints ONE JSON line (rank 0). Besides the driver contract it carries:
-  roofline      sweep-kernel algorithmic bytes / its HIP-event-timed duration vs 8 TB/s; traffic
-                from bench_data/pmc_traffic.json (rocprofv3 PMC, (2*FETCH_SIZE+WRITE_SIZE) KiB)
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if
+--dump-outputs is given, and prints ONE JSON line (rank 0). Besides the driver contract it carries:
+  roofline      sweep-kernel algorithmic bytes / its HIP-event-timed duration (events recorded
+                inside the timed steps) vs 8 TB/s; traffic from bench_data/pmc_traffic.json
+                (rocprofv3 PMC, (2*FETCH_SIZE+WRITE_SIZE) KiB)
+--full adds the legs that take runs of their own, after the timed steps:
+  roofline.measured_read_roof   the read-only probe over the same buffer
   cpu_baseline  the oracle's restatement of Crc32.java (kind "port") on host cores, 1 thread and
                 the process's CPU share, over a DRAM-resident sample (> L3)
   host_path     pinned-host -> HBM -> CRC rate (PCIe-inclusive; never `value`)
   rccl          N > 1: ranks RCCL saw and whether every GPU's gathered vector is right
+  verify        c4: whether the flags name exactly the flipped chunks
+
+--dump-outputs DIR writes what the last timed step left for its caller as DIR/<name>.npy
+(float64, so every 32-bit CRC is exact): crc32 (one GPU), mismatch beside it (c4), or
+gathered_crc32 (N > 1 and the RCCL forms). The workload is seeded, so two builds can be compared
+output for output.
 """
 from __future__ import annotations
 
@@ -60,8 +70,13 @@ def parse():
     ap.add_argument("--grid", type=int, default=None, help="sweep-kernel workgroups (default: one per CU)")
     ap.add_argument("--window", type=int, default=None,
                     help="sweep rounds of at most this many bytes (default: the library's 32 GiB; 0 = one round)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-path", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs that take runs of their own: read-roof "
+                         "probe, CPU baseline, host-resident path, RCCL gather check, c4 flag check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-host-path", action="store_true", help="with --full: skip the host-resident path")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-sample-gib", type=float, default=2.0,
                     help="CPU baseline sample (GiB): several times the host's L3, so it is a DRAM rate")
@@ -338,6 +353,18 @@ def traffic_for(config):
     return p.get("hbm_bytes_per_launch"), p.get("source")
 
 
+def dump_outputs(path, arrays):
+    """Each tensor the timed path handed back, as path/<name>.npy in float64 (exact for 32-bit CRCs)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        if a.dtype == np.int32:
+            a = a.view(np.uint32)
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
+
+
 # ------------------------------------------------------------------ C1 (CPU, one message)
 
 def run_c1(args, result_fd):
@@ -602,6 +629,15 @@ def main():
     kern_ms, launches = sum(kern_each), len(kern_each)
     kern_median_ms = float(sorted(kern_each)[len(kern_each) // 2]) if kern_each else None
     ev_ms = ev0.elapsed_time(ev1)
+    if args.dump_outputs and rank == 0:
+        w = work[0]
+        if mode != "single":
+            outs = {"gathered_crc32": w["gathered"]}
+        elif verify is not None:
+            outs = {"crc32": verify["out"], "mismatch": verify["mism"]}
+        else:
+            outs = {"crc32": w["out"]}
+        dump_outputs(args.dump_outputs, outs)
 
     elapsed = wall
     if dist:
@@ -610,7 +646,7 @@ def main():
         elapsed = float(t.item())
 
     rccl = None
-    if mode != "single":
+    if mode != "single" and args.full:
         # every GPU's gathered vector: its own slot equals its CRCs computed alone (untimed), and in
         # one process all GPUs hold the same vector
         ok = True
@@ -619,7 +655,6 @@ def main():
                 mine = D.crc32_batch(w["buf"], w["off"], w["len"])
                 r = rank + i
                 ok = ok and bool(torch.equal(w["gathered"][r * n:(r + 1) * n], mine))
-                w["out"] = mine
         if mode == "inproc":
             g0 = work[0]["gathered"].cpu()
             ok = ok and all(torch.equal(g0, w["gathered"].cpu()) for w in work[1:])
@@ -635,14 +670,12 @@ def main():
     w0 = work[0]
     with torch.cuda.device(w0["dev"]):
         read_roof = measure_read_roof(torch, D, w0["buf"], w0["buf"].numel(), w0["dev"].index) \
-            if config != "c4" else None
+            if config != "c4" and args.full else None
     verify_ok = None
-    if verify is not None:  # the flags must name exactly the flipped chunks
+    if verify is not None and args.full:  # the flags must name exactly the flipped chunks
         flagged = np.nonzero(verify["mism"].cpu().numpy())[0]
         _, _, cnt = D.crc32_verify(w0["buf"], w0["off"], w0["len"], verify["expected"])  # counter form, untimed
         verify_ok = bool(np.array_equal(flagged, verify["bad"]) and int(cnt.item()) == len(verify["bad"]))
-        w0["out"] = verify["out"]
-    crcs = w0["out"].cpu().numpy().view("uint32")
     value = world * total * args.steps / elapsed / 2**30
     kern_avg_s = kern_ms / max(1, launches) / 1e3
     alg_bytes = total + 4 * n  # chunk bytes read + 4 B CRC written per chunk (offset/len arrays excluded)
@@ -700,12 +733,16 @@ def main():
                             "single-bit flips in 1 % of chunks (seeded)"}),
     }
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_cpu_baseline:
             log(args, "cpu baseline")
             cb = cpu_baseline(w0["buf"], w0["off"], w0["len"], n, args)
             if cb is not None:
                 ref = cb.pop("_out")
+                if mode == "single":
+                    crcs = (w0["out"] if verify is None else verify["out"]).cpu().numpy().view("uint32")
+                else:
+                    crcs = w0["gathered"][:n].cpu().numpy().view("uint32")
                 cb["parity_vs_gpu"] = bool((ref == crcs[:len(ref)]).all())
                 result["cpu_baseline"] = cb
         if not args.no_host_path and config == "c3":

@@ -5,7 +5,7 @@
 set -euo pipefail
 TAG=${TAG:-cfg}
 mkdir -p gpurun_out
-A="--no-cpu-baseline --no-host-path --steps 10 --warmup 2"
+A="--full --no-cpu-baseline --no-host-path --steps 10 --warmup 2"
 timeout -k 10 120 python bench.py --config c1 > gpurun_out/${TAG}_c1.json 2> gpurun_out/${TAG}_c1.err
 timeout -k 10 180 python bench.py --config c2 $A > gpurun_out/${TAG}_c2.json 2> gpurun_out/${TAG}_c2.err
 timeout -k 10 180 python bench.py --config c4 $A > gpurun_out/${TAG}_c4.json 2> gpurun_out/${TAG}_c4.err

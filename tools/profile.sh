@@ -10,9 +10,9 @@
 set -euo pipefail
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-# the kernel-trace pass profiles the bench command itself (default arguments unless
-# BENCH_ARGS is set); the counter passes skip the CPU baseline and host path to stay short
-ARGS=${BENCH_ARGS:-""}
+# the kernel-trace pass profiles the full bench command (--full unless BENCH_ARGS is set);
+# the counter passes are plain runs (no read-roof probe, CPU baseline or host path) to stay short
+ARGS=${BENCH_ARGS:-"--full"}
 PMC_ARGS=${PMC_BENCH_ARGS:-"--steps 5 --warmup 2 --no-cpu-baseline --no-host-path"}
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_kt -o kt -- python3 bench.py $ARGS > gpurun_out/prof_kt.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/prof_fetch -o pmc -- python3 bench.py $PMC_ARGS > gpurun_out/prof_fetch.log 2>&1
