@@ -9,6 +9,7 @@
 
 #include <string.h>
 
+#include "hard_delete.h"
 #include "put_layout.h"
 #include "record_fields.h"
 
@@ -209,9 +210,87 @@ int transform_emit(const uint8_t* region, uint64_t off, const XPlan& x, uint8_t*
   return AMBRYCRC_OK;
 }
 
+// Hard delete: the header work of `verify` alone (version, verifyHeader, checkHeaderConstraints, the
+// message inside rem), then the user-metadata and blob spans (hard_delete.h).
+uint32_t hd_header(const uint8_t* p, uint64_t rem, int* version, ambrycrc::HdSpans* s) {
+  if (rem < 2) return AMBRYCRC_MSG_BAD_LAYOUT;
+  const int v = (int16_t)rd16(p);
+  const uint32_t h = v == 1 ? 34u : v == 2 ? 38u : v == 3 ? 40u : 0u;
+  if (h == 0) return AMBRYCRC_MSG_BAD_VERSION;
+  if (rem < h) return AMBRYCRC_MSG_BAD_LAYOUT;
+  if ((uint64_t)ambrycrc_update(0, p, h - 8) != rd64(p + h - 8)) return AMBRYCRC_MSG_HEADER_CRC;
+  int life = 0;
+  int64_t total;
+  int32_t rel[5];
+  if (v == 3) {
+    life = (int16_t)rd16(p + 2);
+    total = (int64_t)rd64(p + 4);
+    for (int k = 0; k < 5; ++k) rel[k] = (int32_t)rd32(p + 12 + 4 * k);
+  } else {
+    total = (int64_t)rd64(p + 2);
+    rel[0] = -1;
+    for (int k = v == 1 ? 1 : 0; k < 5; ++k) rel[k] = (int32_t)rd32(p + 10 + 4 * (k - (v == 1 ? 1 : 0)));
+  }
+  *version = v;
+  return ambrycrc::hd_header_spans(h, life, total, rel, rem, s);
+}
+
 }  // namespace
 
 extern "C" {
+
+int ambrycrc_hard_delete_message_cpu(uint8_t* region, uint64_t region_len, uint64_t off,
+                                     const ambrycrc_hard_delete_info* recovery, int plan_only, uint32_t* status,
+                                     ambrycrc_hard_delete_info* info) {
+  if (!region || !status) return AMBRYCRC_EINVAL;
+  if (info) memset(info, 0, sizeof *info);
+  if (off > region_len) {
+    *status = AMBRYCRC_MSG_BAD_LAYOUT;
+    return AMBRYCRC_OK;
+  }
+  uint8_t* p = region + off;
+  int hv = 0;
+  ambrycrc::HdSpans s;
+  uint32_t st = hd_header(p, region_len - off, &hv, &s);
+  ambrycrc_hard_delete_info o;
+  memset(&o, 0, sizeof o);
+  if (st == 0 && recovery && recovery->header_version != 0) {  // "Skipping crc check": the records are not read
+    if (ambrycrc::hd_recovery_ok(*recovery, s))
+      o = ambrycrc::hd_info(hv, s, recovery->usermeta_size, recovery->blob_version, recovery->blob_type,
+                            recovery->blob_size);
+    else
+      st = AMBRYCRC_MSG_BAD_RECORD;
+  } else if (st == 0) {  // getUserMetadataInfo / getBlobRecordInfo: the two records' fields and CRCs
+    const uint8_t* um = p + s.um_rel;
+    const uint8_t* bl = p + s.blob_rel;
+    st |= record_check(3, um, s.um_span);
+    if ((uint64_t)ambrycrc_update(0, um, s.um_span - 8) != rd64(um + s.um_span - 8)) st |= AMBRYCRC_MSG_USERMETA_CRC;
+    st |= record_check(4, bl, s.blob_span);
+    if ((uint64_t)ambrycrc_update(0, bl, s.blob_span - 8) != rd64(bl + s.blob_span - 8)) st |= AMBRYCRC_MSG_BLOB_CRC;
+    if (st == 0) {
+      const int bv = (int)rd16(bl);
+      o = ambrycrc::hd_info(hv, s, rd32(um + 2), bv, bv == 1 ? 0 : (int)rd16(bl + 2),
+                            rd64(bl + (bv == 1 ? 2 : bv == 2 ? 4 : 5)));
+    }
+  }
+  *status = st;
+  if (st) return AMBRYCRC_OK;
+  if (info) *info = o;
+  if (plan_only) return AMBRYCRC_OK;
+  // each record: prefix, zero body, CRC = the prefix CRC advanced over the zeros (never read back)
+  uint8_t b[16];
+  uint8_t* q = p + o.start;
+  uint32_t n = ambrycrc::hd_um_prefix(o.usermeta_size, b);
+  memcpy(q, b, n);
+  memset(q + n, 0, o.usermeta_size);
+  ambrycrc::put_be64(q + n + o.usermeta_size, (uint64_t)ambrycrc_zeros(ambrycrc_update(0, b, n), o.usermeta_size));
+  q += s.um_span;
+  n = ambrycrc::hd_blob_prefix(o.blob_version, o.blob_type, o.blob_size, b);
+  memcpy(q, b, n);
+  memset(q + n, 0, o.blob_size);
+  ambrycrc::put_be64(q + n + o.blob_size, (uint64_t)ambrycrc_zeros(ambrycrc_update(0, b, n), o.blob_size));
+  return AMBRYCRC_OK;
+}
 
 int ambrycrc_verify_message_cpu(const uint8_t* region, uint64_t region_len, uint64_t off, uint32_t* status,
                                 uint64_t* msg_end) {

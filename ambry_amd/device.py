@@ -303,6 +303,86 @@ def verify_messages(region, msg_off, stream=None, want_end: bool = True):
     return status, end
 
 
+def _hard_delete_info_dtype():
+    """struct ambrycrc_hard_delete_info (include/ambrycrc.h) as a numpy structured dtype: 32 bytes, no padding.
+    Built on first use and kept as HARD_DELETE_INFO: numpy stays a deferred import in this module, as torch is."""
+    if "HARD_DELETE_INFO" not in globals():
+        import numpy as np
+
+        dt = np.dtype([("blob_size", "<u8"), ("size", "<u8"), ("start", "<u4"), ("usermeta_size", "<u4"),
+                       ("header_version", "<i2"), ("usermeta_version", "<i2"), ("blob_version", "<i2"),
+                       ("blob_type", "<i2")])
+        assert dt.itemsize == 32
+        globals()["HARD_DELETE_INFO"] = dt
+    return globals()["HARD_DELETE_INFO"]
+
+
+def __getattr__(name):
+    if name == "HARD_DELETE_INFO":
+        return _hard_delete_info_dtype()
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def hard_delete_workspace_bytes(m: int) -> int:
+    """Bytes of caller workspace ambrycrc_hard_delete_messages_dev needs for m messages."""
+    return lib().ambrycrc_hard_delete_workspace_bytes(m)
+
+
+def hard_delete_messages(region, msg_off, recovery=None, plan_only: bool = False, stream=None, workspace=None):
+    """GPU hard delete, in place, of the PUT messages starting at msg_off (int64 CUDA tensor) in `region`
+    (ambrycrc_hard_delete_messages_dev): each clean PUT's user-metadata and blob records get zero bodies and
+    fresh CRCs. recovery: the `info` of an earlier plan_only call (uint8[m, 32] CUDA tensor; rows whose
+    header_version is 0 mean "no recovery info") -- the record CRCs are then not read. plan_only: every
+    check, no write.
+
+    Returns (status int32[m] of AMBRYCRC_MSG_* bits, 0 = hard-deleted; info uint8[m, 32] CUDA tensor:
+    rows of HARD_DELETE_INFO, zero for a refused message)."""
+    torch = _torch()
+    if region.dtype != torch.uint8 or not region.is_cuda or not region.is_contiguous():
+        raise TypeError("region must be a contiguous uint8 CUDA tensor")
+    if msg_off.dtype != torch.int64 or not msg_off.is_cuda or not msg_off.is_contiguous() or \
+            msg_off.device != region.device:
+        raise TypeError(f"msg_off must be a contiguous int64 CUDA tensor on {region.device}")
+    m = msg_off.numel()
+    if recovery is not None and (recovery.dtype != torch.uint8 or not recovery.is_cuda or
+                                 not recovery.is_contiguous() or recovery.numel() != 32 * m or
+                                 recovery.device != region.device):
+        raise TypeError(f"recovery must be a contiguous uint8[{m}, 32] CUDA tensor on {region.device}")
+    status = torch.empty(m, dtype=torch.int32, device=region.device)
+    info = torch.empty((m, 32), dtype=torch.uint8, device=region.device)
+    ws, ws_bytes = _workspace(workspace, region.device)
+    check(lib().ambrycrc_hard_delete_messages_dev(_ptr(region), region.numel(), _ptr(msg_off), m, _ptr(recovery),
+                                                  1 if plan_only else 0, _ptr(status), _ptr(info), ws, ws_bytes,
+                                                  ctypes.c_void_p(_stream_handle(stream))),
+          "ambrycrc_hard_delete_messages_dev")
+    return status, info
+
+
+def hard_delete_message_cpu(region, off: int, recovery=None, plan_only: bool = False):
+    """ambrycrc_hard_delete_message_cpu: the same for the one message at `off` of a region in host memory,
+    in place (a writable numpy uint8 array or bytearray). recovery: a HARD_DELETE_INFO record (or None).
+    Returns (status, info: a HARD_DELETE_INFO record, zero when refused)."""
+    import numpy as np
+
+    dtype = _hard_delete_info_dtype()
+    arr = np.frombuffer(region, dtype=np.uint8) if isinstance(region, (bytearray, memoryview)) else region
+    if not isinstance(arr, np.ndarray) or arr.dtype != np.uint8 or not arr.flags.c_contiguous or \
+            not arr.flags.writeable:
+        raise TypeError("region must be a writable contiguous uint8 array or a bytearray")
+    rec = None
+    if recovery is not None:
+        rec = np.zeros(1, dtype=dtype)
+        rec[0] = recovery
+    info = np.zeros(1, dtype=dtype)
+    status = ctypes.c_uint32()
+    check(lib().ambrycrc_hard_delete_message_cpu(ctypes.c_void_p(arr.ctypes.data if arr.nbytes else 0), arr.nbytes,
+                                                 off, None if rec is None else ctypes.c_void_p(rec.ctypes.data),
+                                                 1 if plan_only else 0, ctypes.byref(status),
+                                                 ctypes.c_void_p(info.ctypes.data)),
+          "ambrycrc_hard_delete_message_cpu")
+    return status.value, info[0]
+
+
 def verify_trailed(base, off, length, stream=None):
     """CRC-trailered items on the GPU: item i = base[off[i]:off[i]+len[i]] ends in the big-endian
     8-B CRC of the bytes before it. Returns (mismatch uint8[n], count int32[1])."""

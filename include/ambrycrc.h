@@ -303,6 +303,65 @@ int ambrycrc_transform_messages_dev(const uint8_t* d_region, uint64_t region_len
                                     uint64_t out_cap, uint64_t* d_out_off, uint64_t* d_out_len, uint32_t* d_status,
                                     void* d_ws, size_t ws_bytes, hipStream_t stream);
 
+/* ------------------------------------------------ hard delete of stored PUT messages */
+
+/* HardDeleteRecoveryMetadata without the store key (BlobStoreHardDelete.java:204-299) plus HardDeleteInfo's
+ * offset and size. 32 bytes, no padding. As an input, header_version == 0 means "no recovery info". */
+typedef struct ambrycrc_hard_delete_info {
+  uint64_t blob_size;      /* blobStreamSize */
+  uint64_t size;           /* getHardDeletedMessageSize(): user-metadata record + blob record */
+  uint32_t start;          /* getStartOffsetInMessage(): the user-metadata record's relative offset */
+  uint32_t usermeta_size;
+  int16_t header_version, usermeta_version, blob_version, blob_type;
+} ambrycrc_hard_delete_info;
+
+/* BlobStoreHardDelete.getHardDeleteInfo (BlobStoreHardDelete.java:97-179) for m stored messages at
+ * d_msg_off[i] in [d_region, d_region + region_len), in place: each deleted PUT's user-metadata and
+ * blob records are overwritten with zero bodies and fresh CRCs, as HardDeleteMessageFormatInputStream
+ * writes them (HardDeleteMessageFormatInputStream.java:58-124).
+ * Checks, per message (d_status[i] = AMBRYCRC_MSG_* bits, 0 = hard-deleted):
+ *  - the header first, exactly as ambrycrc_verify_messages_dev: version, verifyHeader
+ *    (MessageFormatRecord.java:1132-1145), checkHeaderConstraints (:985-1030), the message inside the
+ *    region -- AMBRYCRC_MSG_HEADER_CRC / _BAD_VERSION / _BAD_LAYOUT (BlobStoreHardDelete.java:102-120);
+ *  - an update message: AMBRYCRC_MSG_NOT_PUT ("Cleanup operation for a non-PUT record is unsupported",
+ *    :129-131);
+ *  - without recovery info (d_recovery NULL, or d_recovery[i].header_version == 0) the user-metadata and
+ *    blob records only, as the reference deserializes only those (:144-158): each record's version and
+ *    size fields against its span in the header, and its CRC -- AMBRYCRC_MSG_USERMETA_CRC / _BLOB_CRC /
+ *    _BAD_VERSION / _BAD_RECORD, both records reported when both are bad. A corrupt encryption-key or
+ *    blob-properties record, or a corrupt store key, does not stop a hard delete; those bytes stay as
+ *    they are (the key comparison, :121-127, stays with the caller, as in the transform);
+ *  - with recovery info the record CRCs are not read ("Skipping crc check", :160-165) and neither are
+ *    the records; the header is still verified. The recovery fields must be valid -- user-metadata
+ *    version 1, blob version 1..3, blob type < 2 -- and agree with the header's record spans:
+ *    usermeta_size + 14 the user-metadata span, the blob head (10, 12 or 13 B) + blob_size + 8 the
+ *    blob span; otherwise AMBRYCRC_MSG_BAD_RECORD. This is tighter than the reference, which trusts its
+ *    own token: an in-place writer must never write outside the two records.
+ * Writes, for status 0: bytes [off + start, off + start + size) become UserMetadata_Format_V1 (short 1,
+ * int size, zeros, CRC; MessageFormatRecord.java:1619-1635) and the blob record at its stored version
+ * with the same blob type (a V3 record with isCompressed = 0, as serializePartialBlobRecord(..., false)
+ * writes it, :1789-1795), zero body, CRC. Every CRC is a big-endian long with a zero high word, computed
+ * as ambrycrc_zeros(crc(prefix), n): the zero run is never read back. No other byte of the region
+ * changes, and a message with a nonzero status is left untouched. This is in place where the reference
+ * builds a replacement stream for the log to write at the same offsets (HardDeleter.java:655-700).
+ * d_info[i] (nullable): the recovery metadata of message i, all zero for a refused one.
+ * plan_only != 0: every check, d_status and d_info, and no write to the region -- HardDeleter's first
+ * phase (collect the recovery info and persist it, HardDeleter.java:655-683); the second call passes that
+ * d_info as d_recovery and is a pure store pass (:684-700, and the replay after a crash).
+ * Messages must not overlap; the same offset listed twice is allowed. Asynchronous on `stream`, never
+ * synchronizes; may be captured into a HIP graph with a caller workspace (d_ws >=
+ * ambrycrc_hard_delete_workspace_bytes(m)); d_ws NULL uses the stream's default workspace. */
+size_t ambrycrc_hard_delete_workspace_bytes(size_t m);
+int ambrycrc_hard_delete_messages_dev(uint8_t* d_region, uint64_t region_len, const uint64_t* d_msg_off, size_t m,
+                                      const ambrycrc_hard_delete_info* d_recovery /* nullable */, int plan_only,
+                                      uint32_t* d_status, ambrycrc_hard_delete_info* d_info /* nullable */,
+                                      void* d_ws, size_t ws_bytes, hipStream_t stream);
+/* The same for one message of a region in host memory (host-resident logs take this entry per
+ * message): the CLMUL loop for the two record checks, memset for the bodies. */
+int ambrycrc_hard_delete_message_cpu(uint8_t* region, uint64_t region_len, uint64_t off,
+                                     const ambrycrc_hard_delete_info* recovery /* nullable */, int plan_only,
+                                     uint32_t* status, ambrycrc_hard_delete_info* info /* nullable */);
+
 /* ------------------------------------- CRC-trailered records (store files, headers) */
 
 /* Item i = [off[i], off[i] + len[i]) ends in the big-endian 8-B CRC (a long, high word zero)

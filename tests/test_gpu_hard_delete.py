@@ -1,0 +1,200 @@
+"""GPU parity for ambrycrc_hard_delete_messages_dev against the oracle (tests/hard_delete_oracle.py:
+oracle/message_format.py and zlib) and against the CPU entry: status, recovery info and every byte of the
+region after the delete. Every region sits inside a larger tensor with 64 guard bytes of 0xA5 on both sides,
+which must survive."""
+import functools
+
+import numpy as np
+import pytest
+
+import hard_delete_oracle as HD
+from datagen import stream_bytes
+from test_message_format import MF, build_region
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 64
+
+
+def place(region: bytes, shift: int = 0):
+    """(the whole tensor, the region's view in it): guards of 0xA5 around the region, which starts `shift`
+    bytes past a 64-B boundary of the allocation."""
+    import torch
+
+    buf = np.full(GUARD + shift + len(region) + GUARD, 0xA5, dtype=np.uint8)
+    buf[GUARD + shift:GUARD + shift + len(region)] = np.frombuffer(region, dtype=np.uint8)
+    whole = torch.from_numpy(buf).cuda()
+    return whole, whole[GUARD + shift:GUARD + shift + len(region)]
+
+
+def read_back(whole, shift: int, n: int) -> bytes:
+    """The region's bytes, after checking the guards."""
+    h = whole.cpu().numpy()
+    assert (h[:GUARD + shift] == 0xA5).all() and (h[GUARD + shift + n:] == 0xA5).all(), "guard bytes overwritten"
+    return h[GUARD + shift:GUARD + shift + n].tobytes()
+
+
+def to_dev(info):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(info).view(np.uint8).reshape(len(info), 32)).cuda()
+
+
+def run_gpu(gpu, region: bytes, offs, shift=0, recovery=None, plan_only=False):
+    import torch
+
+    whole, r = place(region, shift)
+    o = torch.tensor(np.asarray(offs, dtype=np.int64), device="cuda")
+    status, info = gpu.hard_delete_messages(r, o, recovery=None if recovery is None else to_dev(recovery),
+                                            plan_only=plan_only)
+    torch.cuda.synchronize()
+    return (status.cpu().numpy().view(np.uint32).tolist(), info.cpu().numpy().reshape(-1).view(HD.INFO),
+            read_back(whole, shift, len(region)))
+
+
+@functools.lru_cache(maxsize=None)
+def corrupt_region(seed):
+    region, offs, _ = build_region(n=300, seed=seed, corrupt_frac=0.1, big_every=17)
+    return region, offs, HD.hard_delete(region, offs)
+
+
+@pytest.mark.parametrize("shift", [0, 1, 13, 63])
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_region_matches_oracle_and_cpu(gpu, seed, shift):
+    """PUTs of header V1/V2/V3 (blobs up to 300 KB: ranges split across waves) and update messages, 10 %
+    corrupted, the region at several offsets from a 64-B boundary."""
+    region, offs, (est, einfo, eout) = corrupt_region(seed)
+    deleted, refused, not_put, other = HD.counts(region, offs, est)
+    assert deleted >= 200 and refused >= 20 and not_put >= 20 and other >= 1, (deleted, refused, not_put, other)
+    st, info, out = run_gpu(gpu, region, offs, shift)
+    assert st == est
+    assert np.array_equal(info, einfo)
+    assert out == eout
+    if shift == 0:
+        assert (st, out) == HD.run_cpu(gpu, region, offs)[::2]
+
+
+def test_alignment_grid(gpu):
+    """Messages packed back to back with key lengths 1..16, so the zero spans start on every residue mod 16,
+    crossed with user-metadata and blob sizes around the 16-B piece and the 64-lane store."""
+    msgs = []
+    for klen in range(1, 17):
+        for un in (0, 1, 15, 16, 17):
+            for bn in (0, 1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 255, 256, 4095, 4097):
+                i = len(msgs)
+                msgs.append(MF.put_message(MF.store_key("k" * klen), MF.blob_properties_bytes(bn),
+                                           stream_bytes(500 + i, 0, un).tobytes() if un else b"",
+                                           stream_bytes(9000 + i, 0, bn).tobytes() if bn else b"", version=1 + i % 3))
+    offs = [int(x) for x in np.cumsum([0] + [len(x) for x in msgs[:-1]])]
+    region = b"".join(msgs)
+    est, einfo, eout = HD.hard_delete(region, offs)
+    assert {(o + int(r["start"]) + 6) % 16 for o, r in zip(offs, einfo)} == set(range(16))
+    assert all(s == 0 for s in est)
+    for shift in (0, 5):
+        st, info, out = run_gpu(gpu, region, offs, shift)
+        assert st == est and np.array_equal(info, einfo)
+        assert out == eout
+
+
+def test_share_boundaries(gpu):
+    """One 4 MiB + 1 B blob and one 1 MiB - 3 B blob among 200 small messages: the long ranges are cut into
+    many waves' shares, each with its own unaligned ends."""
+    sizes = {37: (4 << 20) + 1, 150: (1 << 20) - 3}
+    msgs = []
+    for i in range(200):
+        size = sizes.get(i, 50 + (i * 131) % 3000)
+        msgs.append(MF.put_message(MF.store_key("S%d" % i), MF.blob_properties_bytes(size), b"u" * (i % 23),
+                                   stream_bytes(7000 + i, 0, size).tobytes(), version=1 + i % 3))
+    offs = [int(x) for x in np.cumsum([0] + [len(x) for x in msgs[:-1]])]
+    region = b"".join(msgs)
+    est, einfo, eout = HD.hard_delete(region, offs)
+    st, info, out = run_gpu(gpu, region, offs, shift=3)
+    assert st == est == [0] * 200 and np.array_equal(info, einfo)
+    assert out == eout
+
+
+def test_two_phases(gpu):
+    """HardDeleter's two phases (HardDeleter.java:655-700): plan_only leaves the region as it is and returns
+    the recovery info; the second call with that info, on a copy whose blob bodies were damaged in between,
+    deletes every PUT without reading the record CRCs; bad recovery fields are refused."""
+    region, offs, _ = build_region(n=300, seed=2, corrupt_frac=0.0, big_every=17)
+    est, einfo, eout = HD.hard_delete(region, offs)
+    st, info, out = run_gpu(gpu, region, offs, plan_only=True)
+    assert st == est and np.array_equal(info, einfo) and out == region
+    damaged, flipped = HD.flip_blob_bodies(region, offs, info)
+    assert flipped >= 50
+    st, _, out = run_gpu(gpu, damaged, offs)
+    assert sum(1 for s in st if s == MF.BLOB_CRC) == flipped
+    st, info2, out = run_gpu(gpu, damaged, offs, shift=7, recovery=info)
+    assert st == est and np.array_equal(info2, einfo)
+    assert out == eout
+    # one bad field per message, by turns; messages left with good info are still deleted
+    rec = info.copy()
+    puts = [i for i in range(len(offs)) if int(info[i]["header_version"]) and int(info[i]["usermeta_size"])
+            and int(info[i]["blob_size"])]
+    for n, i in enumerate(puts[::2]):
+        rec[i] = HD.bad_recoveries(info[i])[n % 7]
+    exp = HD.hard_delete(region, offs, rec)
+    assert sum(1 for s in exp[0] if s == MF.BAD_RECORD) == len(puts[::2])
+    st, info3, out = run_gpu(gpu, region, offs, recovery=rec)
+    assert st == exp[0] and np.array_equal(info3, exp[1])
+    assert out == exp[2]
+
+
+def test_deleted_messages_verify_clean(gpu):
+    import torch
+
+    region, offs, _ = build_region(n=300, seed=3, corrupt_frac=0.0, big_every=17)
+    whole, r = place(region)
+    o = torch.tensor(np.asarray(offs, dtype=np.int64), device="cuda")
+    st, _ = gpu.hard_delete_messages(r, o)
+    vst, _ = gpu.verify_messages(r, o)
+    torch.cuda.synchronize()
+    st = st.cpu().numpy().view(np.uint32)
+    assert (st == 0).sum() >= 200 and set(st.tolist()) == {0, MF.NOT_PUT}
+    assert (vst.cpu().numpy() == 0).all()
+    assert read_back(whole, 0, len(region)) == HD.hard_delete(region, offs)[2]
+
+
+def test_duplicate_offset_empty_and_single(gpu):
+    import torch
+
+    region, offs, _ = build_region(n=40, seed=6, corrupt_frac=0.1, big_every=10**9)
+    twice = offs + [offs[3], offs[3], offs[20]] + [len(region) + 5, len(region) - 1]  # and two past the region's end
+    est, einfo, eout = HD.hard_delete(region, twice)
+    st, info, out = run_gpu(gpu, region, twice, shift=1)
+    assert st == est and np.array_equal(info, einfo) and out == eout
+    st, info, out = run_gpu(gpu, region, [])
+    assert st == [] and len(info) == 0 and out == region
+    put = next(o for o, s in zip(offs, est) if s == 0)
+    st, info, out = run_gpu(gpu, region, [put])
+    assert (st, out) == HD.hard_delete(region, [put])[::2] and st == [0]
+
+
+def test_graph_capture_and_replay(gpu):
+    """The call only enqueues work, so with a caller workspace it can be captured into a HIP graph (a linear
+    one) and replayed on a fresh copy of the region, byte-exact."""
+    import torch
+
+    region, offs, (est, einfo, eout) = corrupt_region(1)
+    whole, r = place(region)
+    fresh = whole.clone()
+    o = torch.tensor(np.asarray(offs, dtype=np.int64), device="cuda")
+    ws = torch.empty(gpu.hard_delete_workspace_bytes(len(offs)), dtype=torch.uint8, device="cuda")
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        gpu.hard_delete_messages(r, o, workspace=ws)  # loads the kernels outside the capture
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            st, info = gpu.hard_delete_messages(r, o, workspace=ws)
+    torch.cuda.synchronize()
+    for _ in range(2):
+        whole.copy_(fresh)
+        torch.cuda.synchronize()
+        g.replay()
+        torch.cuda.synchronize()
+        assert st.cpu().numpy().view(np.uint32).tolist() == est
+        assert np.array_equal(info.cpu().numpy().reshape(-1).view(HD.INFO), einfo)
+        assert read_back(whole, 0, len(region)) == eout
