@@ -1,6 +1,7 @@
-// ambrycrc.cpp -- host side of libambrycrc: C ABI (include/ambrycrc.h),
-// per-device contexts, kernel launches, host streaming primitives and the
-// pinned-staging host-resident batch path.
+// ambrycrc.cpp -- host side of libambrycrc: the table image, per-device contexts and default
+// workspaces, the batch and message engines' front end (kernel launches), the C ABI
+// (include/ambrycrc.h) of the device-resident entries, the host streaming primitives and the
+// diagnostic knobs. The host-resident entries are in ambrycrc_host.cpp.
 #include "../../include/ambrycrc.h"
 
 #include <hip/hip_runtime.h>
@@ -9,17 +10,9 @@
 #include <string.h>
 
 #include <sched.h>
-#if defined(__x86_64__)
-#include <emmintrin.h>
-#endif
 
 #include <algorithm>
-#include <chrono>
 #include <atomic>
-#include <condition_variable>
-#include <functional>
-#include <memory>
-#include <new>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -133,6 +126,24 @@ std::vector<uint32_t> build_table_image() {
   return img;
 }
 
+// Device pointers a and b of n uint32 each either coincide or do not overlap (in-place
+// continuation d_out == d_crc_in is supported; a shifted overlap is not).
+bool same_or_disjoint(const uint32_t* a, const uint32_t* b, size_t n) {
+  if (!a || !b || a == b) return true;
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x + 4 * n <= y || y + 4 * n <= x;
+}
+
+// The long-record list in the job arrays' space (unused in region mode), `bytes` long: records from
+// byte 64 (at most 4,096), then the piece slots.
+void set_long_list(LongList& l, uint8_t* w, size_t bytes) {
+  l.rec = reinterpret_cast<LongRec*>(w + 64);
+  l.cap = (uint32_t)std::min<size_t>(4096, (bytes - 64) / 2 / sizeof(LongRec));
+  const size_t sb = (64 + l.cap * sizeof(LongRec) + 255) & ~size_t(255);
+  l.slot = reinterpret_cast<uint32_t*>(w + sb);
+  l.pcap = (uint32_t)std::min<size_t>(1u << 30, (bytes - sb) / sizeof(uint32_t));
+}
+
 }  // namespace
 
 namespace ambrycrc {
@@ -142,136 +153,6 @@ std::mutex g_mu;
 DevCtx* g_ctx[kMaxDevices] = {nullptr};
 
 int hip_err(hipError_t e) { return e == hipSuccess ? AMBRYCRC_OK : AMBRYCRC_EHIP; }
-
-// ------------------------------------------------------------ staging copy pool
-// Pageable host chunks (a Netty direct ByteBuf, a FileChannel read buffer) must be
-// memcpy'd into a pinned slab before the DMA engine can move them. One core copies
-// ~25 GB/s, half of PCIe Gen5 x16, so the slab fill is split over a few worker
-// threads (AMBRYCRC_COPY_THREADS, default 8; 1 disables the pool). Process-wide,
-// started on first use; jobs from concurrent callers interleave safely.
-class CopyPool {
- public:
-  static CopyPool& get() {
-    static CopyPool pool;
-    return pool;
-  }
-  int threads() const { return nthreads_; }
-  // Runs fn(0..parts-1) across the workers and the calling thread; returns when all are done.
-  void run(int parts, const std::function<void(int)>& fn) {
-    if (parts <= 1 || workers_.empty()) {
-      for (int i = 0; i < parts; ++i) fn(i);
-      return;
-    }
-    Batch b{&fn, parts};
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      for (int i = 1; i < parts; ++i) queue_.push_back({&b, i});
-    }
-    cv_.notify_all();
-    fn(0);
-    finish_one(b);
-    // help with this batch's remaining parts instead of idling
-    for (;;) {
-      Job j{nullptr, 0};
-      {
-        std::lock_guard<std::mutex> g(mu_);
-        for (size_t q = 0; q < queue_.size(); ++q)
-          if (queue_[q].batch == &b) {
-            j = queue_[q];
-            queue_.erase(queue_.begin() + q);
-            break;
-          }
-      }
-      if (!j.batch) break;
-      (*j.batch->fn)(j.part);
-      finish_one(b);
-    }
-    std::unique_lock<std::mutex> lk(b.mu);
-    b.cv.wait(lk, [&] { return b.left == 0; });
-  }
-  ~CopyPool() {
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      stop_ = true;
-    }
-    cv_.notify_all();
-    for (auto& t : workers_) t.join();
-  }
-
- private:
-  struct Batch {
-    const std::function<void(int)>* fn;
-    int left;
-    std::mutex mu;
-    std::condition_variable cv;
-  };
-  struct Job {
-    Batch* batch;
-    int part;
-  };
-  CopyPool() {
-    int t = 8;
-    if (const char* e = getenv("AMBRYCRC_COPY_THREADS")) t = atoi(e);
-    nthreads_ = std::max(1, std::min(t, 64));
-    try {
-      for (int i = 1; i < nthreads_; ++i) workers_.emplace_back([this] { loop(); });
-    } catch (...) {  // fewer workers than asked (the C ABI does not throw): the parts queue on those started
-    }
-    nthreads_ = (int)workers_.size() + 1;
-  }
-  static void finish_one(Batch& b) {
-    std::lock_guard<std::mutex> g(b.mu);
-    if (--b.left == 0) b.cv.notify_all();
-  }
-  void loop() {
-    for (;;) {
-      Job j;
-      {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [&] { return stop_ || !queue_.empty(); });
-        if (stop_ && queue_.empty()) return;
-        j = queue_.front();
-        queue_.erase(queue_.begin());
-      }
-      (*j.batch->fn)(j.part);
-      finish_one(*j.batch);
-    }
-  }
-  int nthreads_ = 1;
-  std::vector<std::thread> workers_;
-  std::vector<Job> queue_;
-  std::mutex mu_;
-  std::condition_variable cv_;
-  bool stop_ = false;
-};
-
-struct CopyJob {
-  uint8_t* dst;
-  const uint8_t* src;
-  uint64_t n;
-};
-
-// Copies the jobs (disjoint destinations) with the pool: the slab's bytes are split into
-// `parts` equal ranges, each thread copying its range of every job it overlaps.
-void parallel_copy(const std::vector<CopyJob>& jobs, uint64_t total) {
-  if (jobs.empty()) return;
-  CopyPool& pool = CopyPool::get();
-  const int parts = (int)std::min<uint64_t>((uint64_t)pool.threads(), std::max<uint64_t>(1, total >> 20));
-  if (parts <= 1) {
-    for (const CopyJob& j : jobs) memcpy(j.dst, j.src, j.n);
-    return;
-  }
-  std::vector<uint64_t> start(jobs.size() + 1, 0);
-  for (size_t i = 0; i < jobs.size(); ++i) start[i + 1] = start[i] + jobs[i].n;
-  pool.run(parts, [&](int p) {
-    const uint64_t lo = total * (uint64_t)p / (uint64_t)parts, hi = total * (uint64_t)(p + 1) / (uint64_t)parts;
-    size_t i = std::upper_bound(start.begin(), start.end(), lo) - start.begin() - 1;
-    for (; i < jobs.size() && start[i] < hi; ++i) {
-      const uint64_t a = std::max(lo, start[i]), b = std::min(hi, start[i + 1]);
-      if (b > a) memcpy(jobs[i].dst + (a - start[i]), jobs[i].src + (a - start[i]), b - a);
-    }
-  });
-}
 
 DevCtx* ctx_for(int device) {
   if (device < 0 || device >= kMaxDevices) return nullptr;
@@ -463,204 +344,6 @@ int enqueue_batch(DevCtx* c, const uint8_t* base, const uint64_t* off, const uin
   return AMBRYCRC_OK;
 }
 
-// Device pointers a and b of n uint32 each either coincide or do not overlap (in-place
-// continuation d_out == d_crc_in is supported; a shifted overlap is not).
-bool same_or_disjoint(const uint32_t* a, const uint32_t* b, size_t n) {
-  if (!a || !b || a == b) return true;
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x + 4 * n <= y || y + 4 * n <= x;
-}
-
-std::atomic<int> g_cpu_threads{0};  // the process's CPU-leg budget (ambrycrc_set_host_cpu_threads(-1, n)); 0: default
-
-int host_cpu_share() {
-  static const int share = [] {
-    int n = 1;
-    cpu_set_t set;
-    if (sched_getaffinity(0, sizeof(set), &set) == 0) n = std::max(1, CPU_COUNT(&set));
-    // a cgroup v2 CPU quota ("max 100000" when unlimited): a container's share of a larger machine
-    if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-      char q[32] = {0};
-      long long period = 0;
-      if (fscanf(f, "%31s %lld", q, &period) == 2 && strcmp(q, "max") != 0 && period > 0) {
-        const long long quota = atoll(q);
-        if (quota > 0) n = std::min<long long>(n, std::max<long long>(1, (quota + period - 1) / period));
-      }
-      fclose(f);
-    }
-    if (const char* v = getenv("OMP_NUM_THREADS")) {
-      const int t = atoi(v);
-      if (t > 0) n = std::min(n, t);
-    }
-    return std::min(n, 256);
-  }();
-  return share;
-}
-
-int host_cpu_threads(const DevCtx* c) {
-  int t = c ? c->cpu_threads.load(std::memory_order_relaxed) : 0;
-  if (t <= 0) t = g_cpu_threads.load(std::memory_order_relaxed);
-  if (t > 0) return t;
-  if (const char* v = getenv("AMBRYCRC_CPU_THREADS")) {
-    const int e = atoi(v);
-    if (e > 0) return std::min(e, 256);
-  }
-  return std::max(1, host_cpu_share() / 2);
-}
-
-namespace {
-// The calibration for `t` threads: each thread hashes its own slice (16 MiB, 256 MiB in all at most,
-// 1 MiB at least) of a buffer the calling thread wrote with nontemporal stores -- so the timed pass
-// reads DRAM, not the L3, from the pages one writer placed, as a caller's buffer is. Slices each
-// thread wrote itself read 440-679 GiB/s against 172-246 measured on a 2 GiB sample the main thread
-// wrote (r05ao, r05aq: 16 threads, their own slices near them and in their CCDs' L3); a single
-// thread times threads (round 5's first form): 662 against 262.
-double calibrate_cpu(int t) {
-  const size_t slice = std::max<size_t>(1u << 20, std::min<size_t>(16u << 20, ((size_t)256 << 20) / (size_t)t)) &
-                       ~size_t(4095);
-  const size_t total = slice * (size_t)t;
-  std::unique_ptr<uint8_t[]> buf(new (std::nothrow) uint8_t[total]);  // not zero-filled: first touch below
-  if (!buf) return 1.0;
-  // The threads hash their slices once from a common start (all spawned and waiting: spawning
-  // inside the timed span read ~half the rate on a 16-CPU box), timed from the start to the last
-  // thread's end. (A second pass would read the L3.)
-  std::atomic<int> ready{0};
-  std::atomic<int> go{0};
-  std::atomic<int64_t> last_end{0};
-  std::atomic<uint32_t> sink{0};
-  std::vector<std::thread> th;
-  th.reserve(t);
-  {
-    uint8_t* p = buf.get();
-#if defined(__x86_64__)
-    for (size_t i = 0; i < total; i += 16) {  // 16-B aligned (new[] of >= 1 MiB, 4 KiB slices)
-      const __m128i v = _mm_set_epi32((int)(i * 131u), (int)(i * 7u), (int)(i ^ 0x5bd1e995u), (int)i);
-      _mm_stream_si128(reinterpret_cast<__m128i*>(p + i), v);
-    }
-    _mm_sfence();
-#else
-    for (size_t i = 0; i < total; ++i) p[i] = (uint8_t)(i * 131u + 7u);
-#endif
-  }
-  auto body = [&](int k) {
-    const uint8_t* p = buf.get() + slice * (size_t)k;
-    ready.fetch_add(1);
-    while (go.load(std::memory_order_acquire) == 0) std::this_thread::yield();
-    sink ^= ambrycrc_update(0, p, slice);
-    const int64_t e = std::chrono::steady_clock::now().time_since_epoch().count();
-    int64_t cur = last_end.load();
-    while (e > cur && !last_end.compare_exchange_weak(cur, e)) {
-    }
-  };
-  try {
-    for (int k = 0; k < t; ++k) th.emplace_back(body, k);
-  } catch (...) {  // no thread for every slice (the C ABI must not throw): release them, no estimate
-    go.store(1, std::memory_order_release);
-    for (auto& x : th) x.join();
-    return 1.0;
-  }
-  // (the main thread sleeps while it waits: spinning would take a CPU from the hashing threads)
-  while (ready.load() < t) std::this_thread::sleep_for(std::chrono::microseconds(20));
-  const int64_t t0 = std::chrono::steady_clock::now().time_since_epoch().count();
-  go.store(1, std::memory_order_release);
-  for (auto& x : th) x.join();
-  const double best = std::chrono::duration<double>(std::chrono::steady_clock::duration(last_end.load() - t0)).count();
-  if (!(best > 0)) return 1.0;
-  return (double)total / best / (double)(1ull << 30);
-}
-}  // namespace
-
-double host_cpu_gibps(int threads) {
-  static std::mutex mu;
-  static std::vector<std::pair<int, double>> cache;  // (threads, GiB/s), one calibration per budget
-  threads = std::max(1, std::min(threads, 256));
-  std::lock_guard<std::mutex> g(mu);  // one calibration at a time: concurrent ones would share the CPUs
-  for (const auto& e : cache)
-    if (e.first == threads) return e.second;
-  const double r = calibrate_cpu(threads);
-  cache.emplace_back(threads, r);
-  return r;
-}
-
-// The CPU leg's CRC rate on c: as its large calls measured it, else the calibration at c's budget.
-double host_batch_cpu_gibps(const DevCtx* c) {
-  const int t = host_cpu_threads(c);
-  const double r = c ? c->cpu_batch_gibps[std::min(t, DevCtx::kMaxCpuThreads)].load() : -1.0;
-  return r >= 0 ? r : host_cpu_gibps(t);
-}
-
-bool host_take_cpu(DevCtx* c, int device, int pinned, uint64_t bytes) {
-  if (device < 0) return true;
-  if (!c || c->host_policy == 1) return false;
-  if (c->host_policy == 2) return true;
-  if (pinned) return false;
-  const bool cpu = host_batch_cpu_gibps(c) > c->gpu_host_gibps.load();
-  if (bytes >= (64ull << 20) && c->batch_calls.fetch_add(1) % 16 == 15) return !cpu;  // the other leg's rate
-  return cpu;
-}
-
-void host_note_cpu(DevCtx* c, uint64_t bytes, double seconds) {
-  if (!c || bytes < (64ull << 20) || seconds <= 0) return;
-  const double r = (double)bytes / seconds / (double)(1ull << 30);
-  std::atomic<double>& a = c->cpu_batch_gibps[std::min(host_cpu_threads(c), DevCtx::kMaxCpuThreads)];
-  const double old = a.load();
-  a.store(old < 0 ? r : 0.5 * old + 0.5 * r);
-}
-
-// The CPU leg of a message entry before it has been measured: verify parses and CRCs each
-// message, the transform also copies it out (measured on 16 CPUs, r05ag: verify 86 / 142 GiB/s and
-// transform 40 / 60 GiB/s for 4 KiB / 64 KiB PUTs, against a CRC rate of 146-262: ~50 % and ~25 %).
-double host_msg_cpu_gibps(const DevCtx* c, int op) {
-  const double r = c->msg_cpu_gibps[op].load();
-  return r >= 0 ? r
-                : host_cpu_gibps(host_cpu_threads(c)) * 0.01 *
-                      (op == kMsgVerify ? AMBRY_HOST_VERIFY_CPU_PCT : AMBRY_HOST_XFORM_CPU_PCT);
-}
-
-bool host_take_cpu_msg(DevCtx* c, int device, int pinned, int op, uint64_t bytes) {
-  if (device < 0) return true;
-  if (!c || c->host_policy == 1) return false;
-  if (c->host_policy == 2) return true;
-  if (pinned) return false;
-  const bool cpu = host_msg_cpu_gibps(c, op) > c->msg_gpu_gibps[op].load();
-  if (bytes >= (64ull << 20) && c->msg_calls[op].fetch_add(1) % 16 == 15) return !cpu;  // the other leg's rate
-  return cpu;
-}
-
-void host_note_msg(DevCtx* c, int op, bool cpu, uint64_t bytes, double seconds) {
-  if (!c || bytes < (64ull << 20) || seconds <= 0) return;
-  const double r = (double)bytes / seconds / (double)(1ull << 30);
-  std::atomic<double>& a = cpu ? c->msg_cpu_gibps[op] : c->msg_gpu_gibps[op];
-  const double old = a.load();
-  a.store(old < 0 ? r : 0.5 * old + 0.5 * r);
-}
-
-void host_note_gpu(DevCtx* c, uint64_t bytes, double seconds) {
-  if (!c || bytes < (64ull << 20) || seconds <= 0) return;
-  const double r = (double)bytes / seconds / (double)(1ull << 30);
-  c->gpu_host_gibps.store(0.5 * c->gpu_host_gibps.load() + 0.5 * r);
-}
-
-int setup_slabs(DevCtx* c) {
-  if (c->slabs_ready) return AMBRYCRC_OK;
-  // member by member, skipping what an earlier (failed) attempt already allocated
-  auto hhost = [](auto** p, size_t bytes) {
-    return *p || hipHostMalloc(reinterpret_cast<void**>(p), bytes, hipHostMallocDefault) == hipSuccess;
-  };
-  auto hdev = [](auto** p, size_t bytes) { return *p || hipMalloc(reinterpret_cast<void**>(p), bytes) == hipSuccess; };
-  for (auto& s : c->slab) {
-    if (!hhost(&s.h_data, kSlabBytes) || !hhost(&s.h_meta, 2 * kSlabChunks * sizeof(uint64_t)) ||
-        !hhost(&s.h_out, kSlabChunks * sizeof(uint32_t)) || !hdev(&s.d_data, kSlabBytes) ||
-        !hdev(&s.d_meta, 2 * kSlabChunks * sizeof(uint64_t)) || !hdev(&s.d_out, kSlabChunks * sizeof(uint32_t)) ||
-        !(s.d_ws || hipMalloc(&s.d_ws, ws_need(kSlabChunks)) == hipSuccess))
-      return AMBRYCRC_ENOMEM;
-    if (!s.stream && hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess) return AMBRYCRC_EHIP;
-    if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) return AMBRYCRC_EHIP;
-  }
-  c->slabs_ready = true;
-  return AMBRYCRC_OK;
-}
-
 void free_ctx(DevCtx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
@@ -693,37 +376,135 @@ void free_ctx(DevCtx* c) {
     (void)hipEventDestroy(e.a);
     (void)hipEventDestroy(e.b);
   }
-  for (auto& ms : c->msg_slab) {  // allocated member by member on first use; free what exists
-    if (ms.h_off) (void)hipHostFree(ms.h_off);
-    if (ms.h_status) (void)hipHostFree(ms.h_status);
-    if (ms.h_end) (void)hipHostFree(ms.h_end);
-    if (ms.d_off) (void)hipFree(ms.d_off);
-    if (ms.d_status) (void)hipFree(ms.d_status);
-    if (ms.d_end) (void)hipFree(ms.d_end);
-    if (ms.d_ws) (void)hipFree(ms.d_ws);
-  }
-  for (auto& x : c->xform_slab) {
-    if (x.h_life) (void)hipHostFree(x.h_life);
-    if (x.h_out) (void)hipHostFree(x.h_out);
-    if (x.h_olen) (void)hipHostFree(x.h_olen);
-    if (x.d_life) (void)hipFree(x.d_life);
-    if (x.d_out) (void)hipFree(x.d_out);
-    if (x.d_olen) (void)hipFree(x.d_olen);
-    if (x.d_ooff) (void)hipFree(x.d_ooff);
-    if (x.d_ws) (void)hipFree(x.d_ws);
-  }
-  for (auto& s : c->slab) {  // whatever setup_slabs got to, even if it failed part way
-    if (s.h_data) (void)hipHostFree(s.h_data);
-    if (s.h_meta) (void)hipHostFree(s.h_meta);
-    if (s.h_out) (void)hipHostFree(s.h_out);
-    if (s.d_data) (void)hipFree(s.d_data);
-    if (s.d_meta) (void)hipFree(s.d_meta);
-    if (s.d_out) (void)hipFree(s.d_out);
-    if (s.d_ws) (void)hipFree(s.d_ws);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-    if (s.done) (void)hipEventDestroy(s.done);
-  }
+  release_slabs(c);  // whatever the host legs' first uses got to, even if one failed part way
   delete c;
+}
+
+// The device message pipeline (parse -> plan + sweep -> reduce) on `stream`; d_ws holds
+// at least ambrycrc_messages_workspace_bytes(m).
+size_t msg_jobs_bytes(size_t m) {
+  const size_t j = (size_t)kMsgSlots * m;
+  return (j * 2 * sizeof(uint64_t) + j * 2 * sizeof(uint32_t) + j + 255) & ~size_t(255);
+}
+
+// A processor wave finishes a 64-message batch in ~20-40 us (a chain of dependent reads under the
+// streamers' load), so the processors a CU needs grow with its messages; the rest of its waves
+// stream, and too few streamers starve them (a cliff: 3 of 12 at 1 KiB blobs, 0.367 -> 0.438 ms).
+// Measured per messages per CU (r04am-ao, r04au; ms per call): verify form (12 waves) 4 KiB blobs
+// (1,024 per CU) best at 5 (0.377; 8: 0.410), 3 KiB (1,280) at 6 (0.408; 5: 0.418), 2 KiB (1,536)
+// at 6 (0.374; 5: 0.397, 8: 0.387), 1 KiB (2,048) at 8 (0.367), 100 B (4,096) at 9 (0.532; 8:
+// 0.575); copy form (8 waves) at 4 from 128 to 1,024 per CU (4 KiB PUTs 0.663; 3: 0.69, 5: 0.78;
+// 16 KiB PUTs 0.549, 2: 0.562; 32 KiB 0.563, 2: 0.570; r04ba). Verify below 512 per CU (not swept):
+// one processor per 128 messages, at least 2.
+uint32_t fused_proc_waves(const DevCtx* c, size_t m, bool copy) {
+  const int waves = copy ? kFusedWavesCopy : kFusedWavesVerify;
+  const int most = std::min(kFusedProcMax, waves - 2);  // at least two streamers
+  if (c->fused_proc > 0) return (uint32_t)std::min(c->fused_proc, most);
+  const size_t per_cu = m / (size_t)std::max(1, c->num_cu);
+  int p;
+  if (copy) p = 4;
+  else if (per_cu <= 512) p = (int)std::max<size_t>(2, (per_cu + 127) / 128);
+  else p = per_cu <= 1024 ? 5 : per_cu <= 1536 ? 6 : per_cu <= 3072 ? 8 : 9;
+  return (uint32_t)std::min(p, most);
+}
+
+int enqueue_messages(DevCtx* c, const uint8_t* d_region, uint64_t region_len, const uint64_t* d_msg_off, size_t m,
+                     uint32_t* d_status, uint64_t* d_msg_end, void* d_ws, size_t ws_bytes, hipStream_t stream) {
+  const bool region = c->region_mode && region_len > 0 && region_len <= c->region_max * (uint64_t)m &&
+                      msg_jobs_bytes(m) + region_ws_bytes(d_region, region_len, m) <= ws_bytes;
+  MsgStage st;
+  c->last_msg_mode.store(region ? c->region_mode : 0);
+  if (!region) {
+    const int rc = enqueue_messages_parse(c, d_region, region_len, d_msg_off, m, d_status, d_msg_end, d_ws, stream, &st);
+    return rc ? rc : enqueue_messages_check(c, st, stream);
+  }
+  // Region mode: pass 1 sweeps the region into 64-B run sums (kept where job mode keeps its batch
+  // workspace), pass 2 parses every message and assembles its record CRCs from them.
+  st.a.region = d_region;
+  st.a.region_len = region_len;
+  st.a.msg_off = d_msg_off;
+  st.a.m = m;
+  st.a.img = c->d_img;
+  st.a.status = d_status;
+  st.a.msg_end = d_msg_end;
+  st.a.inline_max = 0;
+  st.batch_ws = static_cast<uint8_t*>(d_ws) + msg_jobs_bytes(m);
+  RegionArgs r;
+  const uintptr_t rp = reinterpret_cast<uintptr_t>(d_region);
+  r.base = d_region - (rp & 63u);
+  r.reg0 = rp & 63u;
+  r.reg_end = r.reg0 + region_len;
+  r.lo16 = r.reg0 & ~uint64_t(15);
+  r.hi16 = (r.reg_end - 1) & ~uint64_t(15);
+  r.nsb = region_nsb(d_region, region_len);
+  r.rk = static_cast<uint32_t*>(st.batch_ws);
+  r.img = c->d_img;
+  if (c->region_mode == 2) {  // the two-pass form: runs kernel, then one thread per message
+    // long records (more than region::kLongRuns runs) listed in the job arrays' space, which
+    // region mode does not use: the whole grid takes them after pass 2
+    uint8_t* lw = static_cast<uint8_t*>(d_ws);
+    r.lng.ctr = reinterpret_cast<unsigned long long*>(lw);
+    r.lng.claim = reinterpret_cast<uint32_t*>(lw + 8);
+    set_long_list(r.lng, lw, msg_jobs_bytes(m));
+    if (launch_region_runs(r, c->grid, stream) != hipSuccess ||
+        launch_region_msg(st.a, r, c->num_cu, stream) != hipSuccess)
+      return AMBRYCRC_EHIP;
+    return hip_err(launch_region_long(st.a, r, c->num_cu, stream));
+  }
+  FusedArgs f;
+  f.a = st.a;
+  f.g = r;
+  f.ngroups = (r.nsb + 3) / 4;
+  f.ctl = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(st.batch_ws) + region_rk_bytes(d_region, region_len));
+  f.defer = f.ctl + 64;
+  f.nproc = fused_proc_waves(c, m, false);
+  // long records: listed by the processors (records in the job arrays' space, as the two-pass
+  // form's; the counters in ctl, zeroed with it), taken by region_long_kernel after the tail
+  f.g.lng.ctr = reinterpret_cast<unsigned long long*>(f.ctl + 4);
+  f.g.lng.claim = f.ctl + 6;
+  set_long_list(f.g.lng, static_cast<uint8_t*>(d_ws), msg_jobs_bytes(m));
+  if (hipMemsetAsync(f.ctl, 0, 32, stream) != hipSuccess) return AMBRYCRC_EHIP;
+  return hip_err(launch_region_fused(f, c->num_cu, stream));
+}
+
+int enqueue_messages_parse(DevCtx* c, const uint8_t* d_region, uint64_t region_len, const uint64_t* d_msg_off,
+                           size_t m, uint32_t* d_status, uint64_t* d_msg_end, void* d_ws, hipStream_t stream,
+                           MsgStage* st, const TransformArgs* desc, const uint32_t* gate) {
+  const size_t j = (size_t)kMsgSlots * m;
+  uint8_t* w = static_cast<uint8_t*>(d_ws);
+  MsgArgs& a = st->a;
+  a.gate = gate;
+  a.region = d_region;
+  a.region_len = region_len;
+  a.msg_off = d_msg_off;
+  a.m = m;
+  a.img = c->d_img;
+  a.job_off = reinterpret_cast<uint64_t*>(w);
+  a.job_len = a.job_off + j;
+  a.expected = reinterpret_cast<uint32_t*>(a.job_len + j);
+  uint32_t* crc = a.expected + j;
+  a.crc = crc;
+  a.status = d_status;
+  a.msg_end = d_msg_end;
+  // The class-sized group phase (variant 29) reads the stored CRCs of the records it
+  // takes whole; the parse kernel reads the rest.
+  const bool inline_exp = variant_groups(c->variant);
+  a.inline_max = inline_exp ? batch_small_max(c, j) : 0;
+  st->batch_ws = w + msg_jobs_bytes(m);
+  st->crc = crc;
+  st->j = j;
+  return hip_err(desc ? launch_msg_parse_desc(a, *desc, stream) : launch_msg_parse(a, stream));
+}
+
+int enqueue_messages_check(DevCtx* c, const MsgStage& st, hipStream_t stream, uint8_t* copy_dst,
+                           const uint64_t* copy_off) {
+  const MsgArgs& a = st.a;
+  // copy-through runs the group-phase kernel whatever c's variant, so the stored CRCs of the records
+  // it takes are read there exactly when the parse kernel left them to it (inline_max)
+  const int rc = enqueue_batch(c, a.region, a.job_off, a.job_len, nullptr, st.crc, st.j, st.batch_ws, stream,
+                               a.inline_max ? a.expected : nullptr, copy_dst, copy_off, copy_dst ? a.gate : nullptr);
+  if (rc) return rc;
+  return hip_err(launch_msg_reduce(a, stream));
 }
 
 }  // namespace detail
@@ -959,165 +740,6 @@ int ambrycrc_verify_dev(const uint8_t* d_base, const uint64_t* d_off, const uint
   return hip_err(launch_verify(d_out, d_expected, d_mismatch, d_mismatch_count, (uint32_t)n, stream));
 }
 
-// ambrycrc_batch_host's GPU leg (the dispatcher below picks it or the CPU leg).
-static int batch_host_gpu(DevCtx* c, const void* const* ptrs, const uint64_t* lens, const uint32_t* crc_in,
-                          uint32_t* out, size_t n, int device, int pinned) {
-  std::lock_guard<std::mutex> g(c->mu);
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(device) != hipSuccess) return AMBRYCRC_EHIP;
-  int rc = setup_slabs(c);
-  if (rc) return rc;
-
-  // Pieces: chunks are cut at slab boundaries; pieces of one chunk are combined on the host.
-  struct Piece {
-    size_t chunk;
-    uint64_t pos, len;
-  };
-  std::vector<uint32_t> acc(n, 0u);
-  for (size_t i = 0; i < n; ++i) acc[i] = crc_in ? crc_in[i] : 0u;
-
-  size_t ci = 0;
-  uint64_t cpos = 0;
-  int k = 0;  // slabs issued; slab k uses ring entry k % kSlabs
-  std::vector<Piece> inflight[kSlabs];
-  std::vector<CopyJob> copies;
-  auto drain = [&](int which) -> int {
-    HostSlab& s = c->slab[which];
-    if (inflight[which].empty()) return AMBRYCRC_OK;
-    if (hipEventSynchronize(s.done) != hipSuccess) return AMBRYCRC_EHIP;
-    for (size_t j = 0; j < inflight[which].size(); ++j) {
-      const Piece& p = inflight[which][j];
-      acc[p.chunk] = gf2_mul(acc[p.chunk], host_xpow8(p.len)) ^ s.h_out[j];  // combine(acc, piece, len)
-    }
-    inflight[which].clear();
-    return AMBRYCRC_OK;
-  };
-  while (ci < n) {
-    const int w = k % kSlabs;
-    rc = drain(w);  // the oldest slab in flight: the one we are about to refill
-    if (rc) break;
-    HostSlab& s = c->slab[w];
-    uint64_t used = 0;
-    size_t np = 0;
-    copies.clear();
-    while (ci < n && np < kSlabChunks) {
-      const uint64_t rem = lens[ci] - cpos;
-      const uint64_t room = kSlabBytes - used;
-      if (rem > 0 && room < 16) break;
-      const uint64_t take = std::min(rem, room);
-      if (take > 0 && !ptrs[ci]) {
-        rc = AMBRYCRC_EINVAL;
-        break;
-      }
-      const uint8_t* src = static_cast<const uint8_t*>(ptrs[ci]) + cpos;
-      if (pinned) {
-        if (take && hipMemcpyAsync(s.d_data + used, src, take, hipMemcpyHostToDevice, s.stream) != hipSuccess) {
-          rc = AMBRYCRC_EHIP;
-          break;
-        }
-      } else if (take) {
-        copies.push_back({s.h_data + used, src, take});
-      }
-      s.h_meta[np] = used;
-      s.h_meta[kSlabChunks + np] = take;
-      inflight[w].push_back({ci, cpos, take});
-      ++np;
-      used = (used + take + 15) & ~uint64_t(15);
-      cpos += take;
-      if (cpos >= lens[ci]) {
-        ++ci;
-        cpos = 0;
-      }
-      if (used >= kSlabBytes) break;
-    }
-    if (rc) break;
-    if (!pinned && used) {
-      uint64_t bytes = 0;
-      for (const CopyJob& j : copies) bytes += j.n;
-      parallel_copy(copies, bytes);  // overlaps the DMA of the slabs already issued
-      if (hipMemcpyAsync(s.d_data, s.h_data, std::min<uint64_t>(used, kSlabBytes), hipMemcpyHostToDevice,
-                         s.stream) != hipSuccess) {
-        rc = AMBRYCRC_EHIP;
-        break;
-      }
-    }
-    if (hipMemcpyAsync(s.d_meta, s.h_meta, np * sizeof(uint64_t), hipMemcpyHostToDevice, s.stream) !=
-            hipSuccess ||
-        hipMemcpyAsync(s.d_meta + kSlabChunks, s.h_meta + kSlabChunks, np * sizeof(uint64_t),
-                       hipMemcpyHostToDevice, s.stream) != hipSuccess) {
-      rc = AMBRYCRC_EHIP;
-      break;
-    }
-    rc = enqueue_batch(c, s.d_data, s.d_meta, s.d_meta + kSlabChunks, nullptr, s.d_out, np, s.d_ws, s.stream);
-    if (rc) break;
-    if (hipMemcpyAsync(s.h_out, s.d_out, np * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream) != hipSuccess ||
-        hipEventRecord(s.done, s.stream) != hipSuccess) {
-      rc = AMBRYCRC_EHIP;
-      break;
-    }
-    ++k;
-  }
-  // Oldest slab first: pieces of one chunk must combine in order. On error, still wait
-  // for everything issued so no DMA targets a slab the next call refills.
-  int rc2 = AMBRYCRC_OK;
-  for (int d = 0; d < kSlabs; ++d) {
-    const int r = drain((k + d) % kSlabs);
-    if (!rc2) rc2 = r;
-  }
-  (void)hipSetDevice(prev);
-  if (rc) return rc;
-  if (rc2) return rc2;
-  for (size_t i = 0; i < n; ++i) out[i] = acc[i];
-  return AMBRYCRC_OK;
-}
-
-int ambrycrc_batch_multi(const void* const* ptrs, const uint64_t* lens, const uint32_t* crc_in, uint32_t* out,
-                         size_t n, const int* devices, int ndev, int pinned) {
-  if (ndev <= 0 || ndev > kMaxDevices * 8) return AMBRYCRC_EINVAL;
-  if (n == 0) return AMBRYCRC_OK;
-  if (!ptrs || !lens || !out) return AMBRYCRC_EINVAL;
-  std::vector<int> dev(ndev);
-  for (int g = 0; g < ndev; ++g) {
-    dev[g] = devices ? devices[g] : g;
-    if (!ctx_for(dev[g])) return AMBRYCRC_ENOINIT;
-  }
-  // host-resident dispatch once for the whole batch: the CPU leg when the CPU threads beat every
-  // listed GPU's host path together (auto, pageable), else each range on its GPU
-  {
-    DevCtx* c0 = ctx_for(dev[0]);
-    double gpus = 0;
-    for (int g = 0; g < ndev; ++g) gpus += ctx_for(dev[g])->gpu_host_gibps.load();
-    const int policy = c0->host_policy.load();
-    const bool cpu = policy == 2 || (policy == 0 && !pinned && host_batch_cpu_gibps(c0) > gpus);
-    c0->last_host_path.store(cpu ? 0 : 1);
-    if (cpu) return ambrycrc_batch_cpu(ptrs, lens, crc_in, out, n, host_cpu_threads(c0));
-  }
-  std::vector<size_t> cut(ndev + 1, n);
-  const int src = ambrycrc_shard_by_bytes(lens, n, ndev, cut.data());
-  if (src) return src;
-  std::vector<int> rc(ndev, AMBRYCRC_OK);
-  std::vector<std::thread> th;
-  th.reserve(ndev);
-  for (int r = 0; r < ndev; ++r) {
-    const size_t a = cut[r], b = cut[r + 1];
-    if (a >= b) continue;
-    auto part = [&, r, a, b] {
-      rc[r] = batch_host_gpu(ctx_for(dev[r]), ptrs + a, lens + a, crc_in ? crc_in + a : nullptr, out + a, b - a, dev[r],
-                             pinned);
-    };
-    try {
-      th.emplace_back(part);
-    } catch (...) {  // no thread (the C ABI does not throw): this device's share runs here
-      part();
-    }
-  }
-  for (auto& t : th) t.join();
-  for (int r = 0; r < ndev; ++r)
-    if (rc[r]) return rc[r];
-  return AMBRYCRC_OK;
-}
-
 int ambrycrc_put_crcs(const uint8_t* const* fields, const uint64_t* field_len, const uint8_t* const* prefix,
                       const uint64_t* prefix_len, const uint32_t* blob_crc, const uint64_t* blob_len, size_t n,
                       uint32_t* wire_out, uint32_t* record_out) {
@@ -1131,23 +753,6 @@ int ambrycrc_put_crcs(const uint8_t* const* fields, const uint64_t* field_len, c
     if (record_out) record_out[i] = gf2_mul(ambrycrc_update(0, prefix[i], prefix_len[i]), xb) ^ blob_crc[i];
   }
   return AMBRYCRC_OK;
-}
-
-int ambrycrc_range_checksums_host(const uint8_t* file, uint64_t file_len, const int64_t* first, const int64_t* second,
-                                  size_t n, uint32_t* out, int device) {
-  if (n == 0) return AMBRYCRC_OK;
-  if (!first || !second || !out || (!file && file_len)) return AMBRYCRC_EINVAL;
-  for (size_t i = 0; i < n; ++i)
-    if (first[i] < 0 || second[i] < 0 || first[i] > second[i]) return AMBRYCRC_EINVAL;
-  std::vector<const void*> ptrs(n);
-  std::vector<uint64_t> lens(n);
-  for (size_t i = 0; i < n; ++i) {
-    const uint64_t a = std::min<uint64_t>((uint64_t)first[i], file_len);
-    const uint64_t b = std::min<uint64_t>((uint64_t)second[i], file_len);
-    ptrs[i] = file ? file + a : nullptr;
-    lens[i] = b - a;
-  }
-  return ambrycrc_batch_host(ptrs.data(), lens.data(), nullptr, out, n, device, 0);
 }
 
 int ambrycrc_set_variant(int device, int variant) {
@@ -1305,238 +910,6 @@ size_t ambrycrc_messages_workspace_bytes(size_t m) {
   return msg_jobs_bytes(m) + std::max(ws_need((size_t)kMsgSlots * m), region);
 }
 
-}  // extern "C"
-
-namespace ambrycrc {
-namespace detail {
-
-// The device message pipeline (parse -> plan + sweep -> reduce) on `stream`; d_ws holds
-// at least ambrycrc_messages_workspace_bytes(m).
-size_t msg_jobs_bytes(size_t m) {
-  const size_t j = (size_t)kMsgSlots * m;
-  return (j * 2 * sizeof(uint64_t) + j * 2 * sizeof(uint32_t) + j + 255) & ~size_t(255);
-}
-
-// A processor wave finishes a 64-message batch in ~20-40 us (a chain of dependent reads under the
-// streamers' load), so the processors a CU needs grow with its messages; the rest of its waves
-// stream, and too few streamers starve them (a cliff: 3 of 12 at 1 KiB blobs, 0.367 -> 0.438 ms).
-// Measured per messages per CU (r04am-ao, r04au; ms per call): verify form (12 waves) 4 KiB blobs
-// (1,024 per CU) best at 5 (0.377; 8: 0.410), 3 KiB (1,280) at 6 (0.408; 5: 0.418), 2 KiB (1,536)
-// at 6 (0.374; 5: 0.397, 8: 0.387), 1 KiB (2,048) at 8 (0.367), 100 B (4,096) at 9 (0.532; 8:
-// 0.575); copy form (8 waves) at 4 from 128 to 1,024 per CU (4 KiB PUTs 0.663; 3: 0.69, 5: 0.78;
-// 16 KiB PUTs 0.549, 2: 0.562; 32 KiB 0.563, 2: 0.570; r04ba). Verify below 512 per CU (not swept):
-// one processor per 128 messages, at least 2.
-uint32_t fused_proc_waves(const DevCtx* c, size_t m, bool copy) {
-  const int waves = copy ? kFusedWavesCopy : kFusedWavesVerify;
-  const int most = std::min(kFusedProcMax, waves - 2);  // at least two streamers
-  if (c->fused_proc > 0) return (uint32_t)std::min(c->fused_proc, most);
-  const size_t per_cu = m / (size_t)std::max(1, c->num_cu);
-  int p;
-  if (copy) p = 4;
-  else if (per_cu <= 512) p = (int)std::max<size_t>(2, (per_cu + 127) / 128);
-  else p = per_cu <= 1024 ? 5 : per_cu <= 1536 ? 6 : per_cu <= 3072 ? 8 : 9;
-  return (uint32_t)std::min(p, most);
-}
-
-// The long-record list in the job arrays' space (unused in region mode), `bytes` long: records from
-// byte 64 (at most 4,096), then the piece slots.
-static void set_long_list(LongList& l, uint8_t* w, size_t bytes) {
-  l.rec = reinterpret_cast<LongRec*>(w + 64);
-  l.cap = (uint32_t)std::min<size_t>(4096, (bytes - 64) / 2 / sizeof(LongRec));
-  const size_t sb = (64 + l.cap * sizeof(LongRec) + 255) & ~size_t(255);
-  l.slot = reinterpret_cast<uint32_t*>(w + sb);
-  l.pcap = (uint32_t)std::min<size_t>(1u << 30, (bytes - sb) / sizeof(uint32_t));
-}
-
-int enqueue_messages(DevCtx* c, const uint8_t* d_region, uint64_t region_len, const uint64_t* d_msg_off, size_t m,
-                     uint32_t* d_status, uint64_t* d_msg_end, void* d_ws, size_t ws_bytes, hipStream_t stream) {
-  const bool region = c->region_mode && region_len > 0 && region_len <= c->region_max * (uint64_t)m &&
-                      msg_jobs_bytes(m) + region_ws_bytes(d_region, region_len, m) <= ws_bytes;
-  MsgStage st;
-  c->last_msg_mode.store(region ? c->region_mode : 0);
-  if (!region) {
-    const int rc = enqueue_messages_parse(c, d_region, region_len, d_msg_off, m, d_status, d_msg_end, d_ws, stream, &st);
-    return rc ? rc : enqueue_messages_check(c, st, stream);
-  }
-  // Region mode: pass 1 sweeps the region into 64-B run sums (kept where job mode keeps its batch
-  // workspace), pass 2 parses every message and assembles its record CRCs from them.
-  st.a.region = d_region;
-  st.a.region_len = region_len;
-  st.a.msg_off = d_msg_off;
-  st.a.m = m;
-  st.a.img = c->d_img;
-  st.a.status = d_status;
-  st.a.msg_end = d_msg_end;
-  st.a.inline_max = 0;
-  st.batch_ws = static_cast<uint8_t*>(d_ws) + msg_jobs_bytes(m);
-  RegionArgs r;
-  const uintptr_t rp = reinterpret_cast<uintptr_t>(d_region);
-  r.base = d_region - (rp & 63u);
-  r.reg0 = rp & 63u;
-  r.reg_end = r.reg0 + region_len;
-  r.lo16 = r.reg0 & ~uint64_t(15);
-  r.hi16 = (r.reg_end - 1) & ~uint64_t(15);
-  r.nsb = region_nsb(d_region, region_len);
-  r.rk = static_cast<uint32_t*>(st.batch_ws);
-  r.img = c->d_img;
-  if (c->region_mode == 2) {  // the two-pass form: runs kernel, then one thread per message
-    // long records (more than region::kLongRuns runs) listed in the job arrays' space, which
-    // region mode does not use: the whole grid takes them after pass 2
-    uint8_t* lw = static_cast<uint8_t*>(d_ws);
-    r.lng.ctr = reinterpret_cast<unsigned long long*>(lw);
-    r.lng.claim = reinterpret_cast<uint32_t*>(lw + 8);
-    set_long_list(r.lng, lw, msg_jobs_bytes(m));
-    if (launch_region_runs(r, c->grid, stream) != hipSuccess ||
-        launch_region_msg(st.a, r, c->num_cu, stream) != hipSuccess)
-      return AMBRYCRC_EHIP;
-    return hip_err(launch_region_long(st.a, r, c->num_cu, stream));
-  }
-  FusedArgs f;
-  f.a = st.a;
-  f.g = r;
-  f.ngroups = (r.nsb + 3) / 4;
-  f.ctl = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(st.batch_ws) + region_rk_bytes(d_region, region_len));
-  f.defer = f.ctl + 64;
-  f.nproc = fused_proc_waves(c, m, false);
-  // long records: listed by the processors (records in the job arrays' space, as the two-pass
-  // form's; the counters in ctl, zeroed with it), taken by region_long_kernel after the tail
-  f.g.lng.ctr = reinterpret_cast<unsigned long long*>(f.ctl + 4);
-  f.g.lng.claim = f.ctl + 6;
-  set_long_list(f.g.lng, static_cast<uint8_t*>(d_ws), msg_jobs_bytes(m));
-  if (hipMemsetAsync(f.ctl, 0, 32, stream) != hipSuccess) return AMBRYCRC_EHIP;
-  return hip_err(launch_region_fused(f, c->num_cu, stream));
-}
-
-int enqueue_messages_parse(DevCtx* c, const uint8_t* d_region, uint64_t region_len, const uint64_t* d_msg_off,
-                           size_t m, uint32_t* d_status, uint64_t* d_msg_end, void* d_ws, hipStream_t stream,
-                           MsgStage* st, const TransformArgs* desc, const uint32_t* gate) {
-  const size_t j = (size_t)kMsgSlots * m;
-  uint8_t* w = static_cast<uint8_t*>(d_ws);
-  MsgArgs& a = st->a;
-  a.gate = gate;
-  a.region = d_region;
-  a.region_len = region_len;
-  a.msg_off = d_msg_off;
-  a.m = m;
-  a.img = c->d_img;
-  a.job_off = reinterpret_cast<uint64_t*>(w);
-  a.job_len = a.job_off + j;
-  a.expected = reinterpret_cast<uint32_t*>(a.job_len + j);
-  uint32_t* crc = a.expected + j;
-  a.crc = crc;
-  a.status = d_status;
-  a.msg_end = d_msg_end;
-  // The class-sized group phase (variant 29) reads the stored CRCs of the records it
-  // takes whole; the parse kernel reads the rest.
-  const bool inline_exp = variant_groups(c->variant);
-  a.inline_max = inline_exp ? batch_small_max(c, j) : 0;
-  st->batch_ws = w + msg_jobs_bytes(m);
-  st->crc = crc;
-  st->j = j;
-  return hip_err(desc ? launch_msg_parse_desc(a, *desc, stream) : launch_msg_parse(a, stream));
-}
-
-int enqueue_messages_check(DevCtx* c, const MsgStage& st, hipStream_t stream, uint8_t* copy_dst,
-                           const uint64_t* copy_off) {
-  const MsgArgs& a = st.a;
-  // copy-through runs the group-phase kernel whatever c's variant, so the stored CRCs of the records
-  // it takes are read there exactly when the parse kernel left them to it (inline_max)
-  const int rc = enqueue_batch(c, a.region, a.job_off, a.job_len, nullptr, st.crc, st.j, st.batch_ws, stream,
-                               a.inline_max ? a.expected : nullptr, copy_dst, copy_off, copy_dst ? a.gate : nullptr);
-  if (rc) return rc;
-  return hip_err(launch_msg_reduce(a, stream));
-}
-
-}  // namespace detail
-}  // namespace ambrycrc
-
-namespace {
-
-uint32_t rd_be32(const uint8_t* p) {
-  return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-uint64_t rd_be64(const uint8_t* p) { return ((uint64_t)rd_be32(p) << 32) | rd_be32(p + 4); }
-
-// member by member, skipping what an earlier (failed) attempt already allocated
-template <class T>
-bool host_alloc(T** p, size_t bytes) {
-  return *p || hipHostMalloc(reinterpret_cast<void**>(p), bytes, hipHostMallocDefault) == hipSuccess;
-}
-template <class T>
-bool dev_alloc(T** p, size_t bytes) {
-  return *p || hipMalloc(reinterpret_cast<void**>(p), bytes) == hipSuccess;
-}
-
-// The message-verify members of the host slabs (caller holds c->mu, c's device current).
-int setup_msg_slabs(DevCtx* c) {
-  if (c->msg_slabs_ready) return AMBRYCRC_OK;
-  for (MsgSlab& ms : c->msg_slab)
-    if (!host_alloc(&ms.h_off, kSlabMsgs * sizeof(uint64_t)) || !host_alloc(&ms.h_status, kSlabMsgs * sizeof(uint32_t)) ||
-        !host_alloc(&ms.h_end, kSlabMsgs * sizeof(uint64_t)) || !dev_alloc(&ms.d_off, kSlabMsgs * sizeof(uint64_t)) ||
-        !dev_alloc(&ms.d_status, kSlabMsgs * sizeof(uint32_t)) || !dev_alloc(&ms.d_end, kSlabMsgs * sizeof(uint64_t)) ||
-        !(ms.d_ws || hipMalloc(&ms.d_ws, ambrycrc_messages_workspace_bytes(kSlabMsgs)) == hipSuccess))
-      return AMBRYCRC_ENOMEM;
-  c->msg_slabs_ready = true;
-  return AMBRYCRC_OK;
-}
-
-// The transform members (ambrycrc_transform_messages_host), on top of setup_msg_slabs.
-int setup_xform_slabs(DevCtx* c) {
-  if (c->xform_slabs_ready) return AMBRYCRC_OK;
-  for (XformSlab& x : c->xform_slab)
-    if (!host_alloc(&x.h_life, kSlabMsgs * sizeof(int16_t)) || !dev_alloc(&x.d_life, kSlabMsgs * sizeof(int16_t)) ||
-        !host_alloc(&x.h_out, kXformOutBytes) || !dev_alloc(&x.d_out, kXformOutBytes) ||
-        !host_alloc(&x.h_olen, kSlabMsgs * sizeof(uint64_t)) || !dev_alloc(&x.d_olen, kSlabMsgs * sizeof(uint64_t)) ||
-        !dev_alloc(&x.d_ooff, kSlabMsgs * sizeof(uint64_t)) ||
-        !(x.d_ws || hipMalloc(&x.d_ws, ambrycrc_transform_workspace_bytes(kSlabMsgs)) == hipSuccess))
-      return AMBRYCRC_ENOMEM;
-  c->xform_slabs_ready = true;
-  return AMBRYCRC_OK;
-}
-
-// Bytes from a message's start that the device pipeline may read: the 40-B header window,
-// and, when the header's sizes fit the region, the whole message [0, first record + total).
-// Every early exit of msg_parse_kernel reads the header alone, so a staging copy of this
-// extent gives the same status bits as the whole region would.
-uint64_t message_extent(const uint8_t* p, uint64_t rem) {
-  const uint64_t hdr = std::min<uint64_t>(rem, 40);
-  if (rem < 2) return rem;
-  const int v = (int16_t)(((uint32_t)p[0] << 8) | p[1]);
-  const uint32_t h = v == 1 ? 34u : v == 2 ? 38u : v == 3 ? 40u : 0u;
-  if (h == 0 || rem < h) return hdr;
-  int64_t total;
-  int32_t rel[kMsgSlots];
-  if (v == 1) {
-    total = (int64_t)rd_be64(p + 2);
-    rel[0] = -1;
-    for (int k = 0; k < 4; ++k) rel[k + 1] = (int32_t)rd_be32(p + 10 + 4 * k);
-  } else if (v == 2) {
-    total = (int64_t)rd_be64(p + 2);
-    for (int k = 0; k < 5; ++k) rel[k] = (int32_t)rd_be32(p + 10 + 4 * k);
-  } else {
-    total = (int64_t)rd_be64(p + 4);
-    for (int k = 0; k < 5; ++k) rel[k] = (int32_t)rd_be32(p + 12 + 4 * k);
-  }
-  int64_t first = -1;
-  for (int k = 0; k < kMsgSlots; ++k)
-    if (rel[k] != -1) {
-      first = rel[k];
-      break;
-    }
-  if (total <= 0 || first < 0 || (uint64_t)total > rem || (uint64_t)first > rem - (uint64_t)total) return hdr;
-  return std::max<uint64_t>(hdr, (uint64_t)first + (uint64_t)total);
-}
-
-}  // namespace
-
-namespace ambrycrc {
-namespace detail {
-uint64_t message_extent_of(const uint8_t* p, uint64_t rem) { return message_extent(p, rem); }
-}  // namespace detail
-}  // namespace ambrycrc
-
-extern "C" {
-
 int ambrycrc_verify_messages_dev(const uint8_t* d_region, uint64_t region_len, const uint64_t* d_msg_off, size_t m,
                                  uint32_t* d_status, uint64_t* d_msg_end, void* d_ws, size_t ws_bytes,
                                  hipStream_t stream) {
@@ -1554,472 +927,6 @@ int ambrycrc_verify_messages_dev(const uint8_t* d_region, uint64_t region_len, c
   if (rc) return rc;
   return enqueue_messages(c, d_region, region_len, d_msg_off, m, d_status, d_msg_end, d_ws,
                           ws_bytes ? ws_bytes : need, stream);
-}
-
-// ambrycrc_verify_messages_host's GPU leg.
-static int verify_messages_host_gpu(DevCtx* c, const uint8_t* region, uint64_t region_len, const uint64_t* msg_off,
-                                    size_t m, uint32_t* status, uint64_t* msg_end, int device, int pinned) {
-  std::lock_guard<std::mutex> g(c->mu);
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(device) != hipSuccess) return AMBRYCRC_EHIP;
-  int rc = setup_slabs(c);
-  if (!rc) rc = setup_msg_slabs(c);
-  if (rc) {
-    (void)hipSetDevice(prev);
-    return rc;
-  }
-
-  // Messages in offset order; each slab stages one contiguous span [lo, hi) of the region
-  // that covers every packed message's extent. A message whose extent exceeds a slab gets
-  // a staging buffer of its own.
-  std::vector<size_t> order(m);
-  for (size_t i = 0; i < m; ++i) order[i] = i;
-  if (!std::is_sorted(msg_off, msg_off + m))  // a recovery scan's offsets already are
-    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return msg_off[x] < msg_off[y]; });
-  // Message extents: one header read each, scattered over the region (a cache and TLB miss
-  // apiece), so they are read by the copy pool's threads in parallel.
-  std::vector<uint64_t> ext(m);
-  {
-    CopyPool& pool = CopyPool::get();
-    const int parts = (int)std::min<size_t>((size_t)pool.threads(), std::max<size_t>(1, m / 4096));
-    pool.run(parts, [&](int p) {
-      for (size_t i = m * (size_t)p / (size_t)parts; i < m * (size_t)(p + 1) / (size_t)parts; ++i)
-        ext[i] = msg_off[i] > region_len ? 0 : message_extent(region + msg_off[i], region_len - msg_off[i]);
-    });
-  }
-  auto extent = [&](size_t i) -> uint64_t { return ext[i]; };
-
-  struct Span {
-    uint64_t lo;
-    std::vector<size_t> msgs;
-  };
-  Span inflight[kSlabs];
-  auto drain = [&](int which) -> int {
-    Span& sp = inflight[which];
-    if (sp.msgs.empty()) return AMBRYCRC_OK;
-    if (hipEventSynchronize(c->slab[which].done) != hipSuccess) return AMBRYCRC_EHIP;
-    const MsgSlab& ms = c->msg_slab[which];
-    for (size_t q = 0; q < sp.msgs.size(); ++q) {
-      status[sp.msgs[q]] = ms.h_status[q];
-      if (msg_end) msg_end[sp.msgs[q]] = ms.h_end[q] ? sp.lo + ms.h_end[q] : 0;
-    }
-    sp.msgs.clear();
-    return AMBRYCRC_OK;
-  };
-  std::vector<CopyJob> copies;
-  size_t oi = 0;
-  int k = 0;
-  while (oi < m && !rc) {
-    const size_t first = order[oi];
-    const uint64_t lo = std::min(msg_off[first], region_len);
-    if (extent(first) > kSlabBytes) {  // oversize: its own device buffer, synchronously
-      uint8_t* d_buf = nullptr;
-      uint64_t* d_o = nullptr;
-      uint32_t* d_s = nullptr;
-      uint64_t* d_e = nullptr;
-      void* d_w = nullptr;
-      const uint64_t zero = 0;
-      uint32_t st = 0;
-      uint64_t en = 0;
-      if (hipMalloc(reinterpret_cast<void**>(&d_buf), ext[first]) != hipSuccess ||
-          hipMalloc(reinterpret_cast<void**>(&d_o), 8) != hipSuccess ||
-          hipMalloc(reinterpret_cast<void**>(&d_s), 4) != hipSuccess ||
-          hipMalloc(reinterpret_cast<void**>(&d_e), 8) != hipSuccess ||
-          hipMalloc(&d_w, ambrycrc_messages_workspace_bytes(1)) != hipSuccess) {
-        rc = AMBRYCRC_ENOMEM;
-      } else if (hipMemcpy(d_buf, region + lo, ext[first], hipMemcpyHostToDevice) != hipSuccess ||
-                 hipMemcpy(d_o, &zero, 8, hipMemcpyHostToDevice) != hipSuccess) {
-        rc = AMBRYCRC_EHIP;
-      } else {
-        rc = enqueue_messages(c, d_buf, ext[first], d_o, 1, d_s, d_e, d_w, ambrycrc_messages_workspace_bytes(1), nullptr);
-        if (!rc && (hipMemcpy(&st, d_s, 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                    hipMemcpy(&en, d_e, 8, hipMemcpyDeviceToHost) != hipSuccess))
-          rc = AMBRYCRC_EHIP;
-      }
-      (void)hipFree(d_buf);
-      (void)hipFree(d_o);
-      (void)hipFree(d_s);
-      (void)hipFree(d_e);
-      (void)hipFree(d_w);
-      status[first] = st;
-      if (msg_end) msg_end[first] = en ? lo + en : 0;
-      ++oi;
-      continue;
-    }
-    const int w = k % kSlabs;
-    rc = drain(w);
-    if (rc) break;
-    HostSlab& s = c->slab[w];
-    MsgSlab& ms = c->msg_slab[w];
-    Span& sp = inflight[w];
-    sp.lo = lo;
-    uint64_t hi = lo;
-    while (oi < m && sp.msgs.size() < kSlabMsgs) {
-      const size_t i = order[oi];
-      const uint64_t o = std::min(msg_off[i], region_len);
-      const uint64_t e = o + extent(i);
-      if (ext[i] > kSlabBytes || std::max(hi, e) - lo > kSlabBytes) break;
-      hi = std::max(hi, e);
-      ms.h_off[sp.msgs.size()] = o - lo;
-      sp.msgs.push_back(i);
-      ++oi;
-    }
-    const uint64_t span = hi - lo;
-    // an offset past the region end must stay past the slab end (BAD_LAYOUT either way)
-    for (size_t q = 0; q < sp.msgs.size(); ++q)
-      if (msg_off[sp.msgs[q]] > region_len) ms.h_off[q] = span + 1;
-    if (span) {
-      if (pinned) {
-        if (hipMemcpyAsync(s.d_data, region + lo, span, hipMemcpyHostToDevice, s.stream) != hipSuccess) rc = AMBRYCRC_EHIP;
-      } else {
-        copies.clear();
-        copies.push_back({s.h_data, region + lo, span});
-        parallel_copy(copies, span);  // overlaps the DMA of the slabs already issued
-        if (hipMemcpyAsync(s.d_data, s.h_data, span, hipMemcpyHostToDevice, s.stream) != hipSuccess) rc = AMBRYCRC_EHIP;
-      }
-    }
-    const size_t nm = sp.msgs.size();
-    if (!rc && hipMemcpyAsync(ms.d_off, ms.h_off, nm * sizeof(uint64_t), hipMemcpyHostToDevice, s.stream) != hipSuccess)
-      rc = AMBRYCRC_EHIP;
-    if (!rc)
-      rc = enqueue_messages(c, s.d_data, span, ms.d_off, nm, ms.d_status, ms.d_end, ms.d_ws,
-                            ambrycrc_messages_workspace_bytes(kSlabMsgs), s.stream);
-    if (!rc && (hipMemcpyAsync(ms.h_status, ms.d_status, nm * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream) !=
-                    hipSuccess ||
-                hipMemcpyAsync(ms.h_end, ms.d_end, nm * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream) !=
-                    hipSuccess ||
-                hipEventRecord(s.done, s.stream) != hipSuccess))
-      rc = AMBRYCRC_EHIP;
-    if (rc) {
-      sp.msgs.clear();
-      break;
-    }
-    ++k;
-  }
-  int rc2 = AMBRYCRC_OK;
-  for (int d = 0; d < kSlabs; ++d) {
-    const int r = drain((k + d) % kSlabs);
-    if (!rc2) rc2 = r;
-  }
-  (void)hipSetDevice(prev);
-  return rc ? rc : rc2;
-}
-
-// ambrycrc_transform_messages_host's GPU leg.
-static int transform_messages_host_gpu(DevCtx* c, const uint8_t* region, uint64_t region_len, const uint64_t* msg_off,
-                                       size_t m, const int16_t* life_version, int header_version, uint8_t* out,
-                                       uint64_t out_cap, uint64_t* out_off, uint64_t* out_len, uint32_t* status,
-                                       int device, int pinned) {
-  std::lock_guard<std::mutex> g(c->mu);
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  if (hipSetDevice(device) != hipSuccess) return AMBRYCRC_EHIP;
-  int rc = setup_slabs(c);
-  if (!rc) rc = setup_msg_slabs(c);
-  if (!rc) rc = setup_xform_slabs(c);
-  if (rc) {
-    (void)hipSetDevice(prev);
-    return rc;
-  }
-  // Extents as the verify's (message_extent: a transform reads nothing outside them either).
-  std::vector<uint64_t> ext(m);
-  {
-    CopyPool& pool = CopyPool::get();
-    const int parts = (int)std::min<size_t>((size_t)pool.threads(), std::max<size_t>(1, m / 4096));
-    pool.run(parts, [&](int p) {
-      for (size_t i = m * (size_t)p / (size_t)parts; i < m * (size_t)(p + 1) / (size_t)parts; ++i)
-        ext[i] = msg_off[i] > region_len ? 0 : message_extent(region + msg_off[i], region_len - msg_off[i]);
-    });
-  }
-  // Packing follows ambrycrc_transform_messages_dev over the whole batch: message i's bytes go at
-  // the sum of the transformed lengths of the messages before it, or it gets AMBRYCRC_MSG_NO_ROOM
-  // when they would pass out_cap (that sum still grows by its length, as the device's exclusive
-  // scan of the lengths does). Slabs hold runs of consecutive messages in index order, each run's
-  // span [lo, hi) staged once; the slab's transform packs its messages from 0 in the same order.
-  uint64_t vpos = 0;  // the device scan's running start
-  auto place = [&](size_t i, uint32_t st, uint64_t len, const uint8_t* bytes, std::vector<CopyJob>* jobs) {
-    if (st == 0 && len) {
-      if (vpos + len <= out_cap) {
-        if (out_off) out_off[i] = vpos;
-        out_len[i] = len;
-        status[i] = 0;
-        if (jobs) jobs->push_back({out + vpos, bytes, len});
-        else memcpy(out + vpos, bytes, len);
-      } else {
-        if (out_off) out_off[i] = ~0ull;
-        out_len[i] = 0;
-        status[i] = AMBRYCRC_MSG_NO_ROOM;
-      }
-      vpos += len;
-      return;
-    }
-    if (out_off) out_off[i] = ~0ull;
-    out_len[i] = 0;
-    status[i] = st;
-  };
-  struct Run {
-    size_t i0 = 0, n = 0;
-  };
-  Run inflight[kSlabs];
-  std::vector<CopyJob> jobs;
-  auto drain = [&](int which) -> int {
-    Run& r = inflight[which];
-    if (!r.n) return AMBRYCRC_OK;
-    if (hipEventSynchronize(c->slab[which].done) != hipSuccess) return AMBRYCRC_EHIP;
-    const MsgSlab& ms = c->msg_slab[which];
-    const XformSlab& x = c->xform_slab[which];
-    jobs.clear();
-    uint64_t at = 0, bytes = 0;  // the slab's packed output
-    for (size_t q = 0; q < r.n; ++q) {
-      const uint64_t len = ms.h_status[q] == 0 ? x.h_olen[q] : 0;
-      const size_t before = jobs.size();
-      place(r.i0 + q, ms.h_status[q], len, x.h_out + at, &jobs);
-      if (jobs.size() > before) bytes += len;
-      at += len;
-    }
-    parallel_copy(jobs, bytes);
-    r.n = 0;
-    return AMBRYCRC_OK;
-  };
-  // One message too large for a slab: its own device buffers, synchronously.
-  auto oversize = [&](size_t i) -> int {
-    const uint64_t lo = std::min(msg_off[i], region_len), n = ext[i];
-    const uint64_t cap = ambrycrc_transform_out_bound(n, 1);
-    uint8_t *d_buf = nullptr, *d_out = nullptr;
-    uint64_t *d_o = nullptr, *d_oo = nullptr, *d_ol = nullptr;
-    uint32_t* d_s = nullptr;
-    int16_t* d_l = nullptr;
-    void* d_w = nullptr;
-    std::vector<uint8_t> h;
-    const uint64_t zero = 0;
-    uint32_t st = 0;
-    uint64_t len = 0;
-    int e = AMBRYCRC_OK;
-    if (hipMalloc(reinterpret_cast<void**>(&d_buf), n) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d_out), cap) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d_o), 8) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d_oo), 8) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d_ol), 8) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d_s), 4) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d_l), 2) != hipSuccess ||
-        hipMalloc(&d_w, ambrycrc_transform_workspace_bytes(1)) != hipSuccess) {
-      e = AMBRYCRC_ENOMEM;
-    } else if (hipMemcpy(d_buf, region + lo, n, hipMemcpyHostToDevice) != hipSuccess ||
-               hipMemcpy(d_o, &zero, 8, hipMemcpyHostToDevice) != hipSuccess ||
-               (life_version && hipMemcpy(d_l, life_version + i, 2, hipMemcpyHostToDevice) != hipSuccess)) {
-      e = AMBRYCRC_EHIP;
-    } else {
-      e = ambrycrc_transform_messages_dev(d_buf, n, d_o, 1, life_version ? d_l : nullptr, header_version, d_out, cap,
-                                          d_oo, d_ol, d_s, d_w, ambrycrc_transform_workspace_bytes(1), nullptr);
-      if (!e && (hipMemcpy(&st, d_s, 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                 hipMemcpy(&len, d_ol, 8, hipMemcpyDeviceToHost) != hipSuccess))
-        e = AMBRYCRC_EHIP;
-      if (!e && st == 0) {
-        h.resize(len);
-        if (len && hipMemcpy(h.data(), d_out, len, hipMemcpyDeviceToHost) != hipSuccess) e = AMBRYCRC_EHIP;
-      }
-    }
-    for (void* p : {(void*)d_buf, (void*)d_out, (void*)d_o, (void*)d_oo, (void*)d_ol, (void*)d_s, (void*)d_l, d_w})
-      if (p) (void)hipFree(p);
-    if (!e) place(i, st, st == 0 ? len : 0, h.data(), nullptr);
-    return e;
-  };
-  size_t i = 0;
-  int k = 0;
-  while (i < m && !rc) {
-    if (ext[i] > kSlabBytes) {
-      for (int d = 0; d < kSlabs && !rc; ++d) rc = drain((k + d) % kSlabs);  // keep the output in order
-      if (!rc) rc = oversize(i);
-      ++i;
-      continue;
-    }
-    const int w = k % kSlabs;
-    rc = drain(w);
-    if (rc) break;
-    HostSlab& s = c->slab[w];
-    MsgSlab& ms = c->msg_slab[w];
-    XformSlab& x = c->xform_slab[w];
-    Run& r = inflight[w];
-    r.i0 = i;
-    uint64_t lo = std::min(msg_off[i], region_len), hi = lo + ext[i];
-    size_t n = 0;
-    // A run ends where its span would pass a slab, or where the summed extents of its messages
-    // (each output at most its extent + the growth bound) would pass the slab's output buffer:
-    // messages that share bytes (duplicate offsets) never meet a cap one call over the whole region
-    // would not have.
-    uint64_t outs = 0;
-    while (i + n < m && n < kSlabMsgs && ext[i + n] <= kSlabBytes) {
-      const uint64_t o = std::min(msg_off[i + n], region_len), e = o + ext[i + n];
-      const uint64_t nlo = std::min(lo, o), nhi = std::max(hi, e);
-      const uint64_t nouts = outs + ext[i + n] + AMBRYCRC_TRANSFORM_GROWTH_MAX;
-      if (nhi - nlo > kSlabBytes || (n && nouts > kXformOutBytes)) break;
-      lo = nlo;
-      hi = nhi;
-      outs = nouts;
-      ++n;
-    }
-    const uint64_t span = hi - lo;
-    for (size_t q = 0; q < n; ++q) {
-      ms.h_off[q] = msg_off[i + q] > region_len ? span + 1 : msg_off[i + q] - lo;
-      if (life_version) x.h_life[q] = life_version[i + q];
-    }
-    if (span) {
-      if (pinned) {
-        if (hipMemcpyAsync(s.d_data, region + lo, span, hipMemcpyHostToDevice, s.stream) != hipSuccess) rc = AMBRYCRC_EHIP;
-      } else {
-        jobs.clear();
-        jobs.push_back({s.h_data, region + lo, span});
-        parallel_copy(jobs, span);  // overlaps the DMA and kernels of the slabs already issued
-        if (hipMemcpyAsync(s.d_data, s.h_data, span, hipMemcpyHostToDevice, s.stream) != hipSuccess) rc = AMBRYCRC_EHIP;
-      }
-    }
-    const uint64_t cap = std::min<uint64_t>(kXformOutBytes, std::max(outs, ambrycrc_transform_out_bound(span, n)));
-    if (!rc && (hipMemcpyAsync(ms.d_off, ms.h_off, n * sizeof(uint64_t), hipMemcpyHostToDevice, s.stream) != hipSuccess ||
-                (life_version &&
-                 hipMemcpyAsync(x.d_life, x.h_life, n * sizeof(int16_t), hipMemcpyHostToDevice, s.stream) != hipSuccess)))
-      rc = AMBRYCRC_EHIP;
-    if (!rc)
-      rc = ambrycrc_transform_messages_dev(s.d_data, span, ms.d_off, n, life_version ? x.d_life : nullptr, header_version,
-                                           x.d_out, cap, x.d_ooff, x.d_olen, ms.d_status, x.d_ws,
-                                           ambrycrc_transform_workspace_bytes(kSlabMsgs), s.stream);
-    if (!rc && (hipMemcpyAsync(ms.h_status, ms.d_status, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream) !=
-                    hipSuccess ||
-                hipMemcpyAsync(x.h_olen, x.d_olen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream) != hipSuccess ||
-                hipMemcpyAsync(x.h_out, x.d_out, cap, hipMemcpyDeviceToHost, s.stream) != hipSuccess ||
-                hipEventRecord(s.done, s.stream) != hipSuccess))
-      rc = AMBRYCRC_EHIP;
-    if (rc) break;
-    r.n = n;
-    i += n;
-    ++k;
-  }
-  int rc2 = AMBRYCRC_OK;
-  for (int d = 0; d < kSlabs; ++d) {  // oldest first: the output is packed in message order
-    const int rr = drain((k + d) % kSlabs);
-    if (!rc2) rc2 = rr;
-  }
-  (void)hipSetDevice(prev);
-  return rc ? rc : rc2;
-}
-
-// ---- host-resident dispatch: the CPU leg or the GPU leg per call
-namespace {
-double seconds_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-}
-// The context of a host call (device < 0: none, the CPU leg) and its status.
-int host_ctx(int device, DevCtx** c) {
-  *c = device >= 0 ? ctx_for(device) : nullptr;
-  return device >= 0 && !*c ? AMBRYCRC_ENOINIT : AMBRYCRC_OK;
-}
-}  // namespace
-
-int ambrycrc_batch_host(const void* const* ptrs, const uint64_t* lens, const uint32_t* crc_in, uint32_t* out, size_t n,
-                        int device, int pinned) {
-  if (n == 0) return AMBRYCRC_OK;
-  if (!ptrs || !lens || !out) return AMBRYCRC_EINVAL;
-  DevCtx* c;
-  if (const int rc = host_ctx(device, &c)) return rc;
-  uint64_t bytes = 0;
-  for (size_t i = 0; i < n; ++i) bytes += lens[i];
-  const auto t0 = std::chrono::steady_clock::now();
-  if (host_take_cpu(c, device, pinned, bytes)) {
-    if (c) c->last_host_path.store(0);
-    const int rc = ambrycrc_batch_cpu(ptrs, lens, crc_in, out, n, host_cpu_threads(c));
-    if (rc == AMBRYCRC_OK && device >= 0) host_note_cpu(c, bytes, seconds_since(t0));
-    return rc;
-  }
-  c->last_host_path.store(1);
-  const int rc = batch_host_gpu(c, ptrs, lens, crc_in, out, n, device, pinned);
-  if (rc == AMBRYCRC_OK && !pinned) host_note_gpu(c, bytes, seconds_since(t0));
-  return rc;
-}
-
-int ambrycrc_verify_messages_host(const uint8_t* region, uint64_t region_len, const uint64_t* msg_off, size_t m,
-                                  uint32_t* status, uint64_t* msg_end, int device, int pinned) {
-  if (m == 0) return AMBRYCRC_OK;
-  if (!msg_off || !status || (!region && region_len)) return AMBRYCRC_EINVAL;
-  DevCtx* c;
-  if (const int rc = host_ctx(device, &c)) return rc;
-  const bool cpu = host_take_cpu_msg(c, device, pinned, kMsgVerify, region_len);
-  if (c) c->last_host_path.store(cpu ? 0 : 1);
-  const auto t0 = std::chrono::steady_clock::now();
-  const int rc = cpu ? verify_messages_cpu(region, region_len, msg_off, m, status, msg_end, host_cpu_threads(c))
-                     : verify_messages_host_gpu(c, region, region_len, msg_off, m, status, msg_end, device, pinned);
-  if (rc == AMBRYCRC_OK && !pinned && device >= 0) host_note_msg(c, kMsgVerify, cpu, region_len, seconds_since(t0));
-  return rc;
-}
-
-int ambrycrc_transform_messages_host(const uint8_t* region, uint64_t region_len, const uint64_t* msg_off, size_t m,
-                                     const int16_t* life_version, int header_version, uint8_t* out, uint64_t out_cap,
-                                     uint64_t* out_off, uint64_t* out_len, uint32_t* status, int device, int pinned) {
-  if (m == 0) return AMBRYCRC_OK;
-  if (!msg_off || !out_len || !status || (!region && region_len) || (!out && out_cap) || header_version < 1 ||
-      header_version > 3)
-    return AMBRYCRC_EINVAL;
-  DevCtx* c;
-  if (const int rc = host_ctx(device, &c)) return rc;
-  const bool cpu = host_take_cpu_msg(c, device, pinned, kMsgTransform, region_len);
-  if (c) c->last_host_path.store(cpu ? 0 : 1);
-  const auto t0 = std::chrono::steady_clock::now();
-  const int rc = cpu ? transform_messages_cpu(region, region_len, msg_off, m, life_version, header_version, out, out_cap,
-                                              out_off, out_len, status, host_cpu_threads(c))
-                     : transform_messages_host_gpu(c, region, region_len, msg_off, m, life_version, header_version, out,
-                                                   out_cap, out_off, out_len, status, device, pinned);
-  if (rc == AMBRYCRC_OK && !pinned && device >= 0) host_note_msg(c, kMsgTransform, cpu, region_len, seconds_since(t0));
-  return rc;
-}
-
-int ambrycrc_set_host_policy(int device, int policy) {
-  DevCtx* c = ctx_for(device);
-  if (!c) return AMBRYCRC_ENOINIT;
-  if (policy < 0 || policy > 2) return AMBRYCRC_EINVAL;
-  return c->host_policy.exchange(policy);
-}
-
-int ambrycrc_host_rates(int device, double* cpu_gibps, double* gpu_gibps, int* cpu_threads) {
-  DevCtx* c = device < 0 ? nullptr : ctx_for(device);
-  if (!c && device >= 0) return AMBRYCRC_ENOINIT;
-  const double cpu = host_batch_cpu_gibps(c), gpu = c ? c->gpu_host_gibps.load() : 0.0;
-  if (cpu_gibps) *cpu_gibps = cpu;
-  if (gpu_gibps) *gpu_gibps = gpu;
-  if (cpu_threads) *cpu_threads = host_cpu_threads(c);
-  return cpu > gpu ? 0 : 1;  // auto's leg for pageable bytes, whatever the policy
-}
-
-int ambrycrc_set_host_cpu_threads(int device, int threads) {
-  if (threads < 0 || threads > 256) return AMBRYCRC_EINVAL;
-  if (device < 0) return g_cpu_threads.exchange(threads);
-  DevCtx* c = ctx_for(device);
-  if (!c) return AMBRYCRC_ENOINIT;
-  const int prev = c->cpu_threads.exchange(threads);
-  if (prev != threads)  // the message legs' measured rates were at the old budget (the batch's are kept per budget)
-    for (auto& r : c->msg_cpu_gibps) r.store(-1.0);
-  return prev;
-}
-
-int ambrycrc_host_calibrate(int device, double* cpu_gibps) {
-  DevCtx* c = device < 0 ? nullptr : ctx_for(device);
-  if (!c && device >= 0) return AMBRYCRC_ENOINIT;
-  const double r = host_cpu_gibps(host_cpu_threads(c));
-  if (cpu_gibps) *cpu_gibps = r;
-  return AMBRYCRC_OK;
-}
-
-int ambrycrc_host_msg_rates(int device, int op, double* cpu_gibps, double* gpu_gibps) {
-  DevCtx* c = ctx_for(device);
-  if (!c) return AMBRYCRC_ENOINIT;
-  if (op != kMsgVerify && op != kMsgTransform) return AMBRYCRC_EINVAL;
-  const double cpu = host_msg_cpu_gibps(c, op), gpu = c->msg_gpu_gibps[op].load();
-  if (cpu_gibps) *cpu_gibps = cpu;
-  if (gpu_gibps) *gpu_gibps = gpu;
-  return cpu > gpu ? 0 : 1;
-}
-
-int ambrycrc_last_host_path(int device) {
-  DevCtx* c = ctx_for(device);
-  return c ? c->last_host_path.load() : AMBRYCRC_ENOINIT;
 }
 
 size_t ambrycrc_trailed_workspace_bytes(size_t n) {
@@ -2058,64 +965,6 @@ int ambrycrc_verify_trailed_dev(const uint8_t* d_base, const uint64_t* d_off, co
                          a.inline_max ? a.expected : nullptr);
   if (rc) return rc;
   return hip_err(launch_trailer_verify(a, stream));
-}
-
-int ambrycrc_verify_trailed_host(const void* const* ptrs, const uint64_t* lens, uint8_t* mismatch, size_t n,
-                                 int device, int pinned) {
-  if (n == 0) return AMBRYCRC_OK;
-  if (!ptrs || !lens || !mismatch) return AMBRYCRC_EINVAL;
-  std::vector<uint64_t> body(n);
-  for (size_t i = 0; i < n; ++i) body[i] = lens[i] >= 8 ? lens[i] - 8 : 0;
-  std::vector<uint32_t> crc(n);
-  const int rc = ambrycrc_batch_host(ptrs, body.data(), nullptr, crc.data(), n, device, pinned);
-  if (rc) return rc;
-  for (size_t i = 0; i < n; ++i)
-    mismatch[i] = lens[i] < 8 || rd_be64(static_cast<const uint8_t*>(ptrs[i]) + body[i]) != (uint64_t)crc[i];
-  return AMBRYCRC_OK;
-}
-
-size_t ambrycrc_chain_messages_host(const uint8_t* region, uint64_t region_len, uint64_t start, uint64_t* offs,
-                                    size_t max) {
-  if (!region || !offs) return 0;
-  auto be16 = [](const uint8_t* p) { return (uint32_t)((p[0] << 8) | p[1]); };
-  auto be32 = [](const uint8_t* p) {
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-  };
-  auto be64 = [&](const uint8_t* p) { return ((uint64_t)be32(p) << 32) | be32(p + 4); };
-  size_t cnt = 0;
-  uint64_t off = start;
-  while (cnt < max && off < region_len && region_len - off >= 2) {
-    const uint8_t* p = region + off;
-    const int v = (int16_t)be16(p);
-    const uint32_t h = v == 1 ? 34u : v == 2 ? 38u : v == 3 ? 40u : 0u;
-    if (h == 0 || region_len - off < h) break;
-    if ((uint64_t)ambrycrc_update(0, p, h - 8) != be64(p + h - 8)) break;
-    int64_t total;
-    int32_t rel[5];
-    if (v == 1) {
-      total = (int64_t)be64(p + 2);
-      rel[0] = -1;
-      for (int k = 0; k < 4; ++k) rel[k + 1] = (int32_t)be32(p + 10 + 4 * k);
-    } else if (v == 2) {
-      total = (int64_t)be64(p + 2);
-      for (int k = 0; k < 5; ++k) rel[k] = (int32_t)be32(p + 10 + 4 * k);
-    } else {
-      total = (int64_t)be64(p + 4);
-      for (int k = 0; k < 5; ++k) rel[k] = (int32_t)be32(p + 12 + 4 * k);
-    }
-    int64_t first = -1;
-    for (int k = 0; k < 5; ++k)
-      if (rel[k] != -1) {
-        first = rel[k];
-        break;
-      }
-    if (total <= 0 || first < (int64_t)h || (uint64_t)total > region_len - off ||
-        (uint64_t)first > region_len - off - (uint64_t)total)
-      break;
-    offs[cnt++] = off;
-    off += (uint64_t)first + (uint64_t)total;
-  }
-  return cnt;
 }
 
 long ambrycrc_debug_table_image(uint32_t* out, size_t max_words) {

@@ -1,5 +1,7 @@
-// ambrycrc_ctx.h -- per-device context of libambrycrc and the internal batch entry the C ABI
-// functions share (ambrycrc.cpp, ambrycrc_put.cpp). Internal to the library.
+// ambrycrc_ctx.h -- per-device context of libambrycrc and the internal entries the C ABI functions
+// share: contexts, workspaces and the batch / message engines (ambrycrc.cpp), the serialization
+// pipeline (ambrycrc_put.cpp), the host-resident path's leg policy and staging slabs
+// (ambrycrc_host.cpp) and its CPU legs (ambrycrc_msg_cpu.cpp). Internal to the library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -203,6 +205,9 @@ struct DevCtx {
 };
 
 int hip_err(hipError_t e);
+// Frees c's staging slabs, whichever of their members exist (ambrycrc_host.cpp allocates them on a
+// leg's first use); c's device is current and idle.
+void release_slabs(DevCtx* c);
 // Host-resident dispatch: the CPU threads the CPU leg of device c uses -- its budget
 // (ambrycrc_set_host_cpu_threads), else the process's (the same call with device -1), else
 // AMBRYCRC_CPU_THREADS, else half this process's CPU share (host_cpu_share: affinity, cgroup quota,

@@ -264,31 +264,18 @@ def test_chain_messages_host_under_asan(tmp_path):
     """ambrycrc_chain_messages_host parses untrusted log bytes: built with the library's host code
     under AddressSanitizer/UBSan (-Xarch_host, device code untouched) and run from every start
     offset and on every tail truncation of a region of mixed, partly corrupted messages."""
-    import shutil
     import subprocess
 
+    import native_build
     from test_message_format import build_region
 
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc) or not shutil.which("g++"):
+    if not native_build.have_toolchain():
         pytest.skip("hipcc/g++ not available")
     region, _, _ = build_region(n=40, seed=5, corrupt_frac=0.2, big_every=10**9)
     rf = tmp_path / "region.bin"
     rf.write_bytes(region)
     exe = tmp_path / "chain_asan"
-    csrc = os.path.join(ROOT, "ambry_amd", "csrc")
-    host_o = tmp_path / "host_crc.o"
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fPIC",
-                    "-std=c++17", "-c", os.path.join(csrc, "host_crc.cpp"), "-o", str(host_o)],
-                   check=True, timeout=300)
-    subprocess.run([hipcc, "-O1", "-g", "-std=c++17", "--offload-arch=gfx950",
-                    "-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",
-                    "-Xarch_host", "-fno-sanitize-recover=all", str(host_o),
-                    os.path.join(ROOT, "tests", "native", "chain_asan.cpp"), os.path.join(csrc, "ambrycrc.cpp"),
-                    os.path.join(csrc, "ambrycrc_multi.cpp"), os.path.join(csrc, "crc32_kernels.hip"),
-                    os.path.join(csrc, "message_kernels.hip"), os.path.join(csrc, "ambrycrc_put.cpp"),
-                    os.path.join(csrc, "put_kernels.hip"), os.path.join(csrc, "ambrycrc_msg_cpu.cpp"), "-ldl", "-o",
-                    str(exe)], check=True, timeout=900)
+    native_build.build_sanitized("chain_asan.cpp", exe, tmp_path)
     r = subprocess.run([str(exe), str(rf)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "runs=" in r.stdout
@@ -298,12 +285,11 @@ def test_message_cpu_under_asan(ambry, tmp_path):
     """ambrycrc_verify_message_cpu / ambrycrc_transform_message_cpu parse untrusted bytes: built with
     ASan + UBSan (host side) and run over every message of a region, its truncations and byte
     flips in its header and record heads (tests/native/msg_cpu_asan.cpp)."""
-    import shutil
     import subprocess
 
+    import native_build
     from test_message_format import build_region
 
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     from test_gpu_transform import build_region as transform_region
     from test_message_format import MF, record_level_cases
 
@@ -318,19 +304,7 @@ def test_message_cpu_under_asan(ambry, tmp_path):
     rf3 = tmp_path / "region3.bin"
     rf3.write_bytes(b"".join(m for m, _ in record_level_cases()))
     exe = tmp_path / "msg_cpu_asan"
-    csrc = os.path.join(ROOT, "ambry_amd", "csrc")
-    host_o = tmp_path / "host_crc.o"
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fPIC",
-                    "-std=c++17", "-c", os.path.join(csrc, "host_crc.cpp"), "-o", str(host_o)],
-                   check=True, timeout=300)
-    subprocess.run([hipcc, "-O1", "-g", "-std=c++17", "--offload-arch=gfx950",
-                    "-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",
-                    "-Xarch_host", "-fno-sanitize-recover=all", str(host_o),
-                    os.path.join(ROOT, "tests", "native", "msg_cpu_asan.cpp"), os.path.join(csrc, "ambrycrc.cpp"),
-                    os.path.join(csrc, "ambrycrc_multi.cpp"), os.path.join(csrc, "ambrycrc_put.cpp"),
-                    os.path.join(csrc, "ambrycrc_msg_cpu.cpp"), os.path.join(csrc, "crc32_kernels.hip"),
-                    os.path.join(csrc, "message_kernels.hip"), os.path.join(csrc, "put_kernels.hip"), "-ldl",
-                    "-o", str(exe)], check=True, timeout=900)
+    native_build.build_sanitized("msg_cpu_asan.cpp", exe, tmp_path)
     for f in (rf, rf2, rf3):
         r = subprocess.run([str(exe), str(f)], capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

@@ -451,6 +451,42 @@ def test_host_resident_path(gpu, oracle):
     assert gpu.crc32_batch_host(chunks, device=0, pinned=False, crc_in=cin) == exp2
 
 
+def test_batch_host_error_mid_ring_leaves_ring_clean(gpu):
+    """An error while a staging slab is in flight: 20,001 one-byte pageable chunks, the last with a NULL
+    pointer. A slab takes at most 16,384 pieces (kSlabChunks), so slab 0 is issued and in flight when the
+    host-side check refuses the chunk in slab 1 (no device code ever sees the NULL). The call returns
+    EINVAL, writes nothing, leaves the current device alone and the ring clean: the same chunks with a
+    valid last pointer, run straight after, give zlib's CRCs (crc_in on a few of them)."""
+    import zlib
+
+    from ambry_amd._lib import AMBRYCRC_EINVAL, lib
+
+    torch = _torch()
+    n = 20001
+    mem = stream_bytes(77, 0, n)
+    ptrs = (ctypes.c_void_p * n)(*[mem.ctypes.data + i for i in range(n)])
+    lens = (ctypes.c_uint64 * n)(*([1] * n))
+    out = (ctypes.c_uint32 * n)(*([0xA5A5A5A5] * n))
+    cin = [0] * n
+    for i in (0, 1, 16383, 16384, 20000):  # either side of the slab cut, and the chunk that was refused
+        cin[i] = (i * 0x9E3779B9 + 1) & 0xFFFFFFFF
+    crc_in = (ctypes.c_uint32 * n)(*cin)
+    dev = torch.cuda.current_device()
+    prev = gpu.set_host_policy(0, gpu.HOST_GPU)
+    try:
+        ptrs[n - 1] = None
+        assert lib().ambrycrc_batch_host(ptrs, lens, crc_in, out, n, 0, 0) == AMBRYCRC_EINVAL
+        assert all(v == 0xA5A5A5A5 for v in out)
+        assert torch.cuda.current_device() == dev
+        ptrs[n - 1] = mem.ctypes.data + n - 1
+        assert lib().ambrycrc_batch_host(ptrs, lens, crc_in, out, n, 0, 0) == 0
+        assert gpu.last_host_path(0) == 1
+        assert list(out) == [zlib.crc32(mem[i:i + 1].tobytes(), cin[i]) for i in range(n)]
+        assert torch.cuda.current_device() == dev
+    finally:
+        gpu.set_host_policy(0, prev)
+
+
 @pytest.mark.parametrize("ndev", [1, 3, 16])
 def test_batch_multi(gpu, oracle, ndev):
     """ambrycrc_batch_multi: byte-balanced ranges, one host thread each. The 1-GPU box lists

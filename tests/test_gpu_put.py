@@ -270,10 +270,11 @@ def test_serialize_streamed_after_job_batch(gpu, mf):
 
 
 def test_serialize_back_to_back_one_stream(gpu, mf):
-    """The streamed form's job path runs on the stream's side stream (ring slot per call, the caller's
-    stream waiting on the done signal): 40 calls on one stream -- past the 32 ring slots -- every third
-    batch with long messages (the job path runs), each into its own output, then one synchronize of
-    that stream only. Every output is the oracle's layout."""
+    """Back-to-back serialize calls on one stream share that stream's default workspace (serialize has
+    no side stream: every kernel runs on the caller's): 40 calls, every third batch with long messages
+    (the job path runs next to the streamed form), each into its own output, then one synchronize of
+    that stream only. A call must not read job entries a previous call left in the reused workspace:
+    every output is the oracle's layout."""
     import dataclasses
 
     import torch

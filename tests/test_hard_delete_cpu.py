@@ -144,11 +144,11 @@ def test_hard_delete_cpu_under_asan(tmp_path):
     stand-alone program (tests/native/hard_delete_asan.cpp) that runs it over every message of a region, every
     tail truncation, byte flips in the header and the two record heads, and random recovery structs, and checks
     that no byte outside [start, start + size) ever changes."""
-    import shutil
     import subprocess
 
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc) or not shutil.which("g++"):
+    import native_build
+
+    if not native_build.have_toolchain():
         pytest.skip("hipcc/g++ not available")
     region, _, _ = build_region(n=24, seed=11, corrupt_frac=0.0, big_every=10**9)
     rf = tmp_path / "region.bin"
@@ -156,20 +156,7 @@ def test_hard_delete_cpu_under_asan(tmp_path):
     rf2 = tmp_path / "region2.bin"
     rf2.write_bytes(b"".join(m for _, m in assembled_cases()[::5]))
     exe = tmp_path / "hard_delete_asan"
-    csrc = os.path.join(ROOT, "ambry_amd", "csrc")
-    host_o = tmp_path / "host_crc.o"
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fPIC",
-                    "-std=c++17", "-c", os.path.join(csrc, "host_crc.cpp"), "-o", str(host_o)],
-                   check=True, timeout=300)
-    subprocess.run([hipcc, "-O1", "-g", "-std=c++17", "--offload-arch=gfx950",
-                    "-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",
-                    "-Xarch_host", "-fno-sanitize-recover=all", str(host_o),
-                    os.path.join(ROOT, "tests", "native", "hard_delete_asan.cpp"), os.path.join(csrc, "ambrycrc.cpp"),
-                    os.path.join(csrc, "ambrycrc_multi.cpp"), os.path.join(csrc, "ambrycrc_put.cpp"),
-                    os.path.join(csrc, "ambrycrc_msg_cpu.cpp"), os.path.join(csrc, "ambrycrc_hd.cpp"),
-                    os.path.join(csrc, "crc32_kernels.hip"), os.path.join(csrc, "message_kernels.hip"),
-                    os.path.join(csrc, "put_kernels.hip"), os.path.join(csrc, "hard_delete_kernels.hip"), "-ldl",
-                    "-o", str(exe)], check=True, timeout=900)
+    native_build.build_sanitized("hard_delete_asan.cpp", exe, tmp_path)
     for f in (rf, rf2):
         r = subprocess.run([str(exe), str(f)], capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

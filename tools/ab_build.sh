@@ -20,7 +20,6 @@ cd $tree/ambry_amd
 g++ -O3 -std=c++17 -fPIC -Wall -c -o host_crc.o csrc/host_crc.cpp
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DAMBRY_AB_PROBE_BUILD -DAMBRY_AB_SPLIT_GROUP ${AB_FLAGS:-} \
   -shared -o $ROOT/build/ab/$name/libambrycrc.so host_crc.o \
-  csrc/ambrycrc.cpp csrc/ambrycrc_multi.cpp csrc/ambrycrc_put.cpp csrc/crc32_kernels.hip csrc/message_kernels.hip \
-  csrc/put_kernels.hip csrc/ambrycrc_msg_cpu.cpp csrc/group_kernels.hip -ldl
+  $(ls csrc/*.cpp | grep -v '^csrc/host_crc\.cpp$') csrc/*.hip -ldl
 rm -rf $tree
 echo "built build/ab/$name/libambrycrc.so"
