@@ -12,6 +12,7 @@
 #include "hard_delete.h"
 #include "put_layout.h"
 #include "record_fields.h"
+#include "rekey.h"
 
 namespace {
 
@@ -317,6 +318,55 @@ int ambrycrc_transform_message_cpu(const uint8_t* region, uint64_t region_len, u
   const int rc = transform_emit(region, off, x, out);
   if (rc) return rc;
   *out_len = x.len;
+  return AMBRYCRC_OK;
+}
+
+// BlobIdTransformer.transform of one message (BlobIdTransformer.java:72-87,159-281; rekey.h): the
+// semantics and status bits of ambrycrc_rekey_messages_dev. Every CRC of the output is hashed from the
+// bytes written (the CLMUL loop), the blob record's in one pass with its copy's source still in cache.
+int ambrycrc_rekey_message_cpu(const uint8_t* region, uint64_t region_len, uint64_t off,
+                               const ambrycrc_rekey_desc* desc, const uint8_t* aux, uint64_t aux_len,
+                               int life_version, int header_version, uint8_t* out, uint64_t out_cap,
+                               uint64_t* out_len, uint32_t* status) {
+  if (!region || !desc || !out_len || !status || (!aux && aux_len) || header_version < 1 || header_version > 3 ||
+      life_version > 32767)
+    return AMBRYCRC_EINVAL;
+  *out_len = 0;
+  *status = 0;
+  const ambrycrc_rekey_desc& r = *desc;
+  if (r.key_len == 0) return AMBRYCRC_OK;  // the converter had no key: skipped, not read
+  if (!ambrycrc::rekey_desc_ok(r, aux_len)) {
+    *status = AMBRYCRC_MSG_BAD_DESC;
+    return AMBRYCRC_OK;
+  }
+  Parsed m;
+  m.end = 0;
+  *status = off <= region_len ? verify(region + off, region_len - off, &m) : (uint32_t)AMBRYCRC_MSG_BAD_LAYOUT;
+  if (*status) return AMBRYCRC_OK;
+  ambrycrc_put_desc d;
+  ambrycrc::RekeyFix x;
+  *status = ambrycrc::rekey_plan(region, off, r, life_version >= 0, life_version, header_version, &d, &x);
+  if (*status) return AMBRYCRC_OK;
+  ambrycrc::PutLayout L;
+  if (!ambrycrc::put_layout(d, L)) return AMBRYCRC_EINVAL;  // (rekey_plan checked it)
+  if (!out || L.length > out_cap) {
+    *status = AMBRYCRC_MSG_NO_ROOM;
+    return AMBRYCRC_OK;
+  }
+  const bool repl = r.content_src != ambrycrc::kRekeyKeep;
+  ambrycrc::put_write_fixed(d, L, out);
+  ambrycrc::put_be64(out + L.hsize - 8, (uint64_t)ambrycrc_update(0, out, L.hsize - 8));
+  memcpy(out + L.hsize, aux + d.key_src, d.key_len);
+  if (L.enc_rec) memcpy(out + L.enc_rel, region + d.enckey_src - 6, L.enc_rec);  // the record whole, trailer verified
+  uint8_t* ps = out + L.bp_rel + 2;
+  for (uint32_t j = 0; j < d.props_len; ++j)
+    ps[j] = ambrycrc::rekey_props_byte(x, r, j, j < x.stored_len ? region[d.props_src + j] : 0);
+  ambrycrc::put_be64(ps + d.props_len, (uint64_t)ambrycrc_update(0, out + L.bp_rel, 2ull + d.props_len));
+  memcpy(out + L.um_rel, region + d.usermeta_src - 6, L.um_rec);
+  uint8_t* bc = out + L.blob_rel + 13;
+  if (d.blob_len) memcpy(bc, (repl ? aux : region) + d.blob_src, d.blob_len);
+  ambrycrc::put_be64(bc + d.blob_len, (uint64_t)ambrycrc_update(0, out + L.blob_rel, 13ull + d.blob_len));
+  *out_len = L.length;
   return AMBRYCRC_OK;
 }
 

@@ -1,0 +1,151 @@
+// ambrycrc_rekey.cpp -- batched BlobIdTransformer over a device-resident log region
+// (ambrycrc_rekey_messages_dev): BlobIdTransformer.transform / newMessage
+// (ambry-replication/.../BlobIdTransformer.java:72-87,159-281). Kernels: rekey_kernels.hip; the shared
+// per-message logic: rekey.h; the per-message CPU entry: ambrycrc_msg_cpu.cpp. A plain pipeline on the
+// caller's stream -- no speculation, no side stream: verify, plan, place, write, copy.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "../../include/ambrycrc.h"
+#include "ambrycrc_ctx.h"
+#include "crc32_kernels.h"
+#include "rekey.h"
+
+using namespace ambrycrc;
+using namespace ambrycrc::detail;
+
+namespace {
+
+// Workspace of m messages: put descriptors (80 B), RekeyFix (16 B), the content CRC jobs (off, len) and
+// the 4m copy jobs (src, dst, len, cost) of 8 B, then the 4-B arrays: the placement scan's per-message
+// output, the content CRCs, the copy scan's per-job output. After it one shared area, used in turn by
+// the verify, the placement scan, the content CRC batch and the copy scan (same stream, one after the other).
+size_t rekey_own_bytes(size_t m) {
+  return (m * (sizeof(ambrycrc_put_desc) + sizeof(RekeyFix) + 2 * sizeof(uint64_t) +
+               (size_t)kRekeySlots * 4 * sizeof(uint64_t) + (2 + (size_t)kRekeySlots) * sizeof(uint32_t)) +
+          255) &
+         ~size_t(255);
+}
+
+// The plan kernel's exclusive scan of len[0..n) into byte_start (no small-chunk classes), as the
+// serializer's copy plan uses it.
+PlanArgs scan_args(const uint64_t* off, const uint64_t* len, size_t n, void* ws, uint32_t* out) {
+  PlanArgs p;
+  p.gate = nullptr;
+  p.off = off;
+  p.len = len;
+  p.crc_in = nullptr;
+  p.n = (uint32_t)n;
+  p.byte_start = static_cast<uint64_t*>(ws);
+  const size_t blocks = (n + kPlanPerBlock - 1) / kPlanPerBlock;
+  p.block_sum = p.byte_start + n + 1;
+  p.block_small = p.block_sum + blocks;
+  p.small_total = p.block_small + blocks;
+  p.small_idx = reinterpret_cast<uint32_t*>(p.small_total + 5);
+  p.crc_stage = nullptr;
+  p.out = out;
+  p.small_max = 0;
+  return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t ambrycrc_rekey_workspace_bytes(size_t m) {
+  return rekey_own_bytes(m) + std::max(ambrycrc_messages_workspace_bytes(m), ws_need((size_t)kRekeySlots * m));
+}
+
+uint64_t ambrycrc_rekey_out_bound(uint64_t region_len, size_t m, uint64_t aux_len) {
+  const uint64_t b = ambrycrc_transform_out_bound(region_len, m);
+  return aux_len > UINT64_MAX - b ? UINT64_MAX : b + aux_len;
+}
+
+int ambrycrc_rekey_messages_dev(const uint8_t* d_region, uint64_t region_len, const uint64_t* d_msg_off, size_t m,
+                                const ambrycrc_rekey_desc* d_desc, const uint8_t* d_aux, uint64_t aux_len,
+                                const int16_t* d_life_version, int header_version, uint8_t* d_out, uint64_t out_cap,
+                                uint64_t* d_out_off, uint64_t* d_out_len, uint32_t* d_status, void* d_ws,
+                                size_t ws_bytes, hipStream_t stream) {
+  static_assert(sizeof(ambrycrc_rekey_desc) == 40, "ambrycrc_rekey_desc");
+  if (m == 0) return AMBRYCRC_OK;
+  if (!d_region || !d_msg_off || !d_desc || !d_out || !d_out_len || !d_status || (!d_aux && aux_len) ||
+      header_version < 1 || header_version > 3 || (size_t)kMsgSlots * m >= (1ull << 31))
+    return AMBRYCRC_EINVAL;
+  DevCtx* c = ctx_current();
+  if (!c) return AMBRYCRC_ENOINIT;
+  WsLease lease;
+  int rc = lease.acquire(c, stream, &d_ws, ws_bytes, ambrycrc_rekey_workspace_bytes(m));
+  if (rc) return rc;
+  const size_t j = (size_t)kRekeySlots * m;
+  uint8_t* w = static_cast<uint8_t*>(d_ws);
+  RekeyArgs a;
+  a.region = d_region;
+  a.region_len = region_len;
+  a.msg_off = d_msg_off;
+  a.m = m;
+  a.rdesc = d_desc;
+  a.aux = d_aux ? d_aux : d_region;  // aux_len 0: every span is refused or empty; never dereferenced
+  a.aux_len = aux_len;
+  a.life = d_life_version;
+  a.header_version = header_version;
+  a.desc = reinterpret_cast<ambrycrc_put_desc*>(w);
+  a.fix = reinterpret_cast<RekeyFix*>(a.desc + m);
+  a.cjob_off = reinterpret_cast<uint64_t*>(a.fix + m);
+  a.cjob_len = a.cjob_off + m;
+  a.cp_src = a.cjob_len + m;
+  a.cp_dst = a.cp_src + j;
+  a.cp_len = a.cp_dst + j;
+  a.cp_cost = a.cp_len + j;
+  uint32_t* scan_out = reinterpret_cast<uint32_t*>(a.cp_cost + j);
+  uint32_t* ccrc = scan_out + m;
+  uint32_t* cp_scan_out = ccrc + m;
+  a.ccrc = ccrc;
+  a.out_len = d_out_len;
+  a.status = d_status;
+  a.out = d_out;
+  a.img = c->d_img;
+  void* shared = w + rekey_own_bytes(m);
+
+  // 1. the message verify (job mode), into d_status
+  MsgStage ms;
+  rc = enqueue_messages_parse(c, d_region, region_len, d_msg_off, m, d_status, nullptr, shared, stream, &ms);
+  if (rc) return rc;
+  rc = enqueue_messages_check(c, ms, stream);
+  if (rc) return rc;
+  // 2. refusals, output descriptors and lengths
+  if (launch_rekey_plan(a, stream) != hipSuccess) return AMBRYCRC_EHIP;
+  // 3. packed placement: exclusive scan of the lengths, then the transform's place step (NO_ROOM
+  //    for a message past out_cap, which still advances the running offset)
+  const PlanArgs p = scan_args(d_msg_off, d_out_len, m, shared, scan_out);
+  if (launch_plan(p, stream) != hipSuccess) return AMBRYCRC_EHIP;
+  TransformArgs t;
+  memset(&t, 0, sizeof t);
+  t.m = m;
+  t.desc = a.desc;
+  t.out_len = d_out_len;
+  t.out_off = d_out_off;
+  t.status = d_status;
+  t.out_cap = out_cap;
+  if (launch_transform_place(t, p.byte_start, stream) != hipSuccess) return AMBRYCRC_EHIP;
+  // 4. the replacement contents' CRCs (one job a message over aux; most are empty and read nothing),
+  //    then header, record heads, properties and every trailer
+  rc = enqueue_batch(c, a.aux, a.cjob_off, a.cjob_len, nullptr, ccrc, m, shared, stream);
+  if (rc) return rc;
+  if (launch_rekey_write(a, stream) != hipSuccess) return AMBRYCRC_EHIP;
+  // 5. the bodies, balanced by cost over the whole grid
+  const PlanArgs q = scan_args(a.cp_dst, a.cp_cost, j, shared, cp_scan_out);
+  if (launch_plan(q, stream) != hipSuccess) return AMBRYCRC_EHIP;
+  CopyArgs ca;
+  ca.src = a.cp_src;
+  ca.dst_off = a.cp_dst;
+  ca.len = a.cp_len;
+  ca.start = q.byte_start;
+  ca.n = (uint32_t)j;
+  ca.dst = d_out;
+  ca.gate = nullptr;
+  return hip_err(launch_gather_copy(ca, c->num_cu * 8, stream));
+}
+
+}  // extern "C"

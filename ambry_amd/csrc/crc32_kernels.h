@@ -339,6 +339,42 @@ hipError_t launch_transform_merge(const TransformArgs& a, hipStream_t s);
 hipError_t launch_xform_signal(const uint32_t* xfail, uint32_t* done, uint32_t seq, hipStream_t s);
 hipError_t launch_props_fix(const TransformArgs& a, hipStream_t s);
 
+// BlobIdTransformer (rekey_kernels.hip, ambrycrc_rekey.cpp): verified stored messages -> put
+// descriptors with the caller's new keys -> header, record heads, properties and trailers written by
+// one thread per message, bodies by the gather copy.
+struct RekeyFix;  // rekey.h
+constexpr uint32_t kRekeySlots = 4;  // copy jobs per message: key, encryption-key record, user-metadata record, blob content
+struct RekeyArgs {
+  const uint8_t* region;
+  uint64_t region_len;
+  const uint64_t* msg_off;            // [m]
+  uint64_t m;
+  const ::ambrycrc_rekey_desc* rdesc; // [m] the caller's
+  const uint8_t* aux;
+  uint64_t aux_len;
+  const int16_t* life;                // [m] or null
+  int header_version;                 // of the output
+  ::ambrycrc_put_desc* desc;          // [m] rekey_plan_kernel (header_version 0: nothing to write)
+  RekeyFix* fix;                      // [m]
+  uint64_t* out_len;                  // [m]
+  uint32_t* status;                   // [m] in: the verify's bits; out: the final status
+  // the replacement contents' CRC batch over aux: job i = message i's content (empty when it keeps
+  // the stored one or is not written), ccrc[i] its CRC
+  uint64_t* cjob_off;                 // [m]
+  uint64_t* cjob_len;                 // [m]
+  const uint32_t* ccrc;               // [m]
+  uint8_t* out;
+  // rekey_write_kernel: the copy jobs, slot-major (job k*m + i = slot k of message i), absolute
+  // source addresses (region or aux), as CopyArgs
+  uint64_t* cp_src;                   // [4m]
+  uint64_t* cp_dst;
+  uint64_t* cp_len;
+  uint64_t* cp_cost;
+  const uint32_t* img;
+};
+hipError_t launch_rekey_plan(const RekeyArgs& a, hipStream_t s);
+hipError_t launch_rekey_write(const RekeyArgs& a, hipStream_t s);
+
 // ---- copy-mode serialization of small messages by streaming the output (round 6)
 // put_stream_kernel: a wave per message writes the whole message -- header and record heads computed,
 // fields and blob gathered from their sources, trailers zero -- in 16-B output pieces (four 1 KiB wave

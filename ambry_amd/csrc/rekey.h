@@ -1,0 +1,172 @@
+// rekey.h -- BlobIdTransformer's per-message decisions and its BlobProperties re-encoding
+// (ambry-replication/.../BlobIdTransformer.java:72-87,159-281), shared by the device batch
+// (rekey_kernels.hip, ambrycrc_rekey.cpp) and the per-message CPU entry (ambrycrc_msg_cpu.cpp).
+//
+// A verified PUT is re-serialized through PutMessageFormatInputStream (:259-262) with
+//   the converted store key                                 (newKey, :162, :260)
+//   the stored encryption key and user metadata             (:170-175)
+//   BlobProperties re-encoded at VERSION_5 with the new key's accountId / containerId (:249-254) and,
+//   for a metadata blob, the composite's total size (:242)
+//   the stored blob content, or for a MetadataBlob the caller's rewritten content (:183-247)
+// Everything here reads only inside the spans the verify established.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/ambrycrc.h"
+#include "put_layout.h"
+#include "record_fields.h"
+
+namespace ambrycrc {
+
+__host__ __device__ inline uint64_t ld_be64(const uint8_t* p) {
+  uint64_t v;
+  __builtin_memcpy(&v, p, 8);
+  return __builtin_bswap64(v);
+}
+
+constexpr uint64_t kRekeyKeep = ~0ull;       // ambrycrc_rekey_desc::content_src: keep the stored content
+constexpr uint32_t kSerdeBlobSize = 19;      // offset of blobSize in the SerDe bytes (version, ttl, private, creationTime)
+
+// How a stored BlobPropertiesSerDe payload becomes the re-keyed VERSION_5 one, and what the write
+// step needs of the stored blob record (16 B a message in the workspace).
+struct RekeyFix {
+  uint32_t stored_len;  // stored payload bytes
+  uint32_t enc_pos;     // offset of the `encrypted` byte (stored version >= 3), else 0
+  uint32_t acct_pos;    // offset of the accountId short in the VERSION_5 bytes (containerId follows)
+  uint8_t version;      // stored SerDe version 1..5
+  uint8_t priv, enc;    // canonical bytes (`== 1`)
+  uint8_t blob_head;    // stored blob record head: 10, 12 or 13 B (Blob_Format_V1 / V2 / V3)
+};
+static_assert(sizeof(RekeyFix) == 16, "RekeyFix");
+
+// The descriptor's own spans: the new key and the replacement content inside [0, aux_len), the
+// content no longer than a Java array. Checked before the message is looked at.
+__host__ __device__ inline bool rekey_desc_ok(const ambrycrc_rekey_desc& r, uint64_t aux_len) {
+  if (r.key_src > aux_len || r.key_len > aux_len - r.key_src) return false;
+  if (r.content_src == kRekeyKeep) return true;
+  return r.content_len <= 0x7FFFFFFFull && r.content_src <= aux_len && r.content_len <= aux_len - r.content_src;
+}
+
+// Byte j of the re-keyed VERSION_5 payload, from the stored payload's byte j (`stored`; anything
+// when j >= stored_len): the transform's re-encoding (record_fields.h: SerDe version 5, canonical
+// private / encrypted bytes, the fields older versions lack appended as their defaults), then
+// blobSize when given and the new accountId / containerId.
+__host__ __device__ inline uint8_t rekey_props_byte(const RekeyFix& x, const ambrycrc_rekey_desc& r, uint32_t j,
+                                                    uint8_t stored) {
+  uint8_t b = j < x.stored_len ? stored : 0;  // appended fields: encrypted 0, null strings (int 0)
+  if (j == 0) b = 0;
+  else if (j == 1) b = 5;
+  else if (j == kSerdePrivate) b = x.priv;
+  else if (x.enc_pos && j == x.enc_pos) b = x.enc;
+  if (r.props_blob_size >= 0 && j >= kSerdeBlobSize && j < kSerdeBlobSize + 8)
+    b = (uint8_t)((uint64_t)r.props_blob_size >> (8 * (kSerdeBlobSize + 7 - j)));
+  if (j >= x.acct_pos && j < x.acct_pos + 4) {
+    const uint32_t ids = (uint32_t)(uint16_t)r.account_id << 16 | (uint16_t)r.container_id;
+    b = (uint8_t)(ids >> (8 * (x.acct_pos + 3 - j)));
+  }
+  return b;
+}
+
+__host__ __device__ inline uint32_t rekey_props_len(const RekeyFix& x) {
+  uint8_t a[kPropsAppendixMax];
+  return x.stored_len + props_appendix(x.version, a);
+}
+
+// BlobIdTransformer.newMessage for the message at region + off, which the verify passed clean (its
+// header and every record lie inside the region, the record checks hold) and whose descriptor
+// rekey_desc_ok accepted: 0 and the output's put descriptor (key_src and, with replacement content,
+// blob_src are offsets in aux, the other sources offsets in the region; out_off left 0) and *x, or
+// the refusal. have_life: write life_version as given, else the stored header's (0 for V1 / V2).
+__host__ __device__ inline uint32_t rekey_plan(const uint8_t* region, uint64_t off, const ambrycrc_rekey_desc& r,
+                                               bool have_life, int life_version, int header_version,
+                                               ambrycrc_put_desc* d, RekeyFix* x) {
+  const uint8_t* p = region + off;
+  const uint32_t v = ld_be16(p);
+  const uint32_t hs = v == 1 ? 34u : v == 2 ? 38u : 40u;
+  int32_t rel[5];
+  int64_t total;
+  uint32_t life = 0;
+  if (v == 3) {
+    life = ld_be16(p + 2);
+    total = (int64_t)ld_be64(p + 4);
+    for (int k = 0; k < 5; ++k) rel[k] = (int32_t)ld_be32(p + 12 + 4 * k);
+  } else {
+    total = (int64_t)ld_be64(p + 2);
+    rel[0] = -1;
+    for (int k = v == 1 ? 1 : 0; k < 5; ++k) rel[k] = (int32_t)ld_be32(p + 10 + 4 * (k - (v == 1 ? 1 : 0)));
+  }
+  const int32_t enc = rel[0], bp = rel[1], upd = rel[2], um = rel[3], blob = rel[4];
+  if (upd != -1 || bp == -1 || um == -1 || blob == -1) return AMBRYCRC_MSG_NOT_PUT;  // "Only 'put' records are valid"
+  // the deserializers' field reads, as the transform's (message_kernels.hip transform_describe)
+  const int64_t first = enc != -1 ? enc : bp;
+  const int64_t end = first + total;
+  bool ok = first >= (int64_t)hs;
+  uint32_t enc_len = 0;
+  if (enc != -1) {
+    enc_len = ld_be32(p + enc + 2);
+    ok = ok && (int64_t)enc + 6 + enc_len + 8 == bp;
+  }
+  const int64_t props_len = (int64_t)um - bp - 2 - 8;
+  const uint32_t um_len = ld_be32(p + um + 2);
+  ok = ok && props_len >= 0 && (int64_t)um + 6 + um_len + 8 == blob;
+  PropsFields pf;
+  ok = ok && props_parse<true>(p + bp + 2, (uint64_t)props_len, &pf) == 0;
+  const uint32_t bv = ld_be16(p + blob);
+  uint32_t head = 0, type = 0, comp = 0;
+  uint64_t size = 0;
+  if (bv == 1) {
+    size = ld_be64(p + blob + 2);
+    head = 10;
+  } else if (bv == 2) {
+    type = ld_be16(p + blob + 2);
+    size = ld_be64(p + blob + 4);
+    head = 12;
+  } else if (bv == 3) {
+    type = ld_be16(p + blob + 2);
+    comp = p[blob + 4] == 1 ? 1u : 0u;
+    size = ld_be64(p + blob + 5);
+    head = 13;
+  } else {
+    ok = false;
+  }
+  ok = ok && type < 2 && size <= 0x7FFFFFFFull && (int64_t)blob + head + (int64_t)size + 8 == end;
+  if (!ok) return AMBRYCRC_MSG_BAD_RECORD;
+  if (!pf.ascii) return AMBRYCRC_MSG_NOT_ENCODABLE;
+  const bool repl = r.content_src != kRekeyKeep;
+  if (repl && type == 0) return AMBRYCRC_MSG_BAD_DESC;        // content is rewritten for a MetadataBlob only (:183)
+  if (!repl && type == 1) return AMBRYCRC_MSG_NEEDS_CONTENT;  // ... and always for one (:185-247)
+  x->stored_len = (uint32_t)props_len;
+  x->version = (uint8_t)pf.version;
+  x->priv = pf.priv_raw == 1 ? 1 : 0;
+  x->enc = pf.enc_raw == 1 ? 1 : 0;
+  x->enc_pos = pf.version >= 3 ? pf.enc_pos : 0u;
+  // accountId: V1 stores none (the appendix starts with it), V2 ends with the two shorts, from V3 on
+  // they sit right before the `encrypted` byte
+  x->acct_pos = pf.version == 1 ? (uint32_t)props_len : pf.version == 2 ? (uint32_t)props_len - 4 : pf.enc_pos - 4;
+  x->blob_head = (uint8_t)head;
+  __builtin_memset(d, 0, sizeof *d);
+  const bool keep_enc = enc != -1 && header_version >= 2;
+  d->key_src = r.key_src;
+  d->key_len = r.key_len;
+  d->enckey_src = keep_enc ? off + enc + 6 : 0;
+  d->enckey_len = keep_enc ? (int32_t)enc_len : -1;
+  d->props_src = off + bp + 2;
+  d->props_len = rekey_props_len(*x);
+  d->usermeta_src = off + um + 6;
+  d->usermeta_len = um_len;
+  d->blob_src = repl ? r.content_src : off + blob + head;
+  d->blob_len = repl ? r.content_len : size;
+  d->life_version = (int16_t)(have_life ? life_version : (int)life);
+  d->blob_type = (int16_t)type;
+  d->compressed = (uint8_t)comp;
+  d->header_version = (uint8_t)header_version;
+  PutLayout L;
+  if (!put_layout(*d, L)) {  // a relative offset past a Java int
+    d->header_version = 0;
+    return AMBRYCRC_MSG_BAD_RECORD;
+  }
+  return 0;
+}
+
+}  // namespace ambrycrc

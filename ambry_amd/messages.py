@@ -227,3 +227,92 @@ def transform_host(region, msg_off, header_version: int = 3, life_version=None, 
     del keep
     used = int((oo[st == 0] + ol[st == 0]).max()) if (st == 0).any() else 0
     return out[:used].tobytes(), oo.view(np.int64), ol.view(np.int64), st
+
+
+# ------------------------------------------------------------------ re-keying (BlobIdTransformer)
+# status bits added by the re-key (include/ambrycrc.h)
+MSG_NEEDS_CONTENT = 1 << 14
+MSG_BAD_DESC = 1 << 15
+
+REKEY_KEEP = 0xFFFFFFFFFFFFFFFF  # ambrycrc_rekey_desc.content_src: keep the stored blob content
+
+# numpy mirror of struct ambrycrc_rekey_desc (40 bytes): what the caller's StoreKeyConverter decided for
+# one message. key_src / content_src are offsets into one auxiliary buffer; key_len 0 skips the message.
+REKEY_DESC_DTYPE = np.dtype([
+    ("key_src", "<u8"), ("content_src", "<u8"), ("content_len", "<u8"), ("props_blob_size", "<i8"),
+    ("key_len", "<u4"), ("account_id", "<i2"), ("container_id", "<i2")])
+assert REKEY_DESC_DTYPE.itemsize == 40
+
+
+def rekey_out_bound(region_len: int, m: int, aux_len: int) -> int:
+    """ambrycrc_rekey_out_bound: an output capacity that never yields MSG_NO_ROOM for m messages that share
+    no region bytes, when every aux byte is used by at most one descriptor."""
+    return int(lib().ambrycrc_rekey_out_bound(region_len, m, aux_len))
+
+
+def rekey_workspace_bytes(m: int) -> int:
+    return int(lib().ambrycrc_rekey_workspace_bytes(m))
+
+
+def rekey_message_cpu(region, off: int, desc, aux, header_version: int = 3, life=None, out_cap=None):
+    """ambrycrc_rekey_message_cpu: BlobIdTransformer.transform of the message at `off` of a host buffer.
+    desc: one REKEY_DESC_DTYPE record; aux: the bytes its offsets refer to.
+    Returns (status bits, the re-keyed message; None when refused, b"" when skipped)."""
+    buf = np.frombuffer(region, dtype=np.uint8) if not isinstance(region, np.ndarray) else region
+    ax = np.frombuffer(aux, dtype=np.uint8) if not isinstance(aux, np.ndarray) else aux
+    d = np.zeros(1, dtype=REKEY_DESC_DTYPE)
+    d[0] = desc
+    cap = out_cap if out_cap is not None else rekey_out_bound(buf.size - min(off, buf.size), 1, ax.size)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    st, n = ctypes.c_uint32(0), ctypes.c_uint64(0)
+    check(lib().ambrycrc_rekey_message_cpu(ctypes.c_void_p(buf.ctypes.data if buf.size else 0), buf.size, off,
+                                           ctypes.c_void_p(d.ctypes.data),
+                                           ctypes.c_void_p(ax.ctypes.data if ax.size else 0), ax.size,
+                                           -1 if life is None else int(life), header_version,
+                                           ctypes.c_void_p(out.ctypes.data), cap, ctypes.byref(n), ctypes.byref(st)),
+          "ambrycrc_rekey_message_cpu")
+    return st.value, (out[:n.value].tobytes() if st.value == 0 else None)
+
+
+def rekey_dev(region, msg_off, descs, aux, header_version: int = 3, life_version=None, out=None, stream=None,
+              workspace=None):
+    """ambrycrc_rekey_messages_dev -- BlobIdTransformer.transform for a batch of stored messages in HBM:
+    every clean PUT re-serialized at `header_version` under the new store key of descs[i] (a uint8 CUDA
+    tensor holding the REKEY_DESC_DTYPE array; the keys and replacement contents in `aux`, a uint8 CUDA
+    tensor), packed in order into `out` (default: rekey_out_bound bytes). life_version: an int16 CUDA
+    tensor, or None for the stored ones. workspace: a CUDA tensor of rekey_workspace_bytes(m) bytes
+    (needed to capture the call into a graph), or None for the stream's default one.
+    Returns (out, out_off int64[m] (-1: not written), out_len int64[m], status int32[m])."""
+    import torch
+
+    from .device import _stream_handle, _workspace
+
+    if region.dtype != torch.uint8 or not region.is_cuda:
+        raise TypeError("region must be a uint8 CUDA tensor")
+    dev = region.device
+    if msg_off.dtype != torch.int64 or not msg_off.is_cuda or not msg_off.is_contiguous() or msg_off.device != dev:
+        raise TypeError("msg_off must be a contiguous int64 CUDA tensor on the region's device")
+    m = msg_off.numel()
+    if descs.dtype != torch.uint8 or not descs.is_cuda or not descs.is_contiguous() or descs.device != dev or \
+            descs.numel() != m * REKEY_DESC_DTYPE.itemsize:
+        raise TypeError("descs must be a contiguous uint8 CUDA tensor of m 40-byte descriptors")
+    if aux.dtype != torch.uint8 or not aux.is_cuda or not aux.is_contiguous() or aux.device != dev:
+        raise TypeError("aux must be a contiguous uint8 CUDA tensor on the region's device")
+    if life_version is not None and (life_version.dtype != torch.int16 or life_version.numel() != m
+                                     or not life_version.is_cuda or not life_version.is_contiguous()):
+        raise TypeError("life_version must be a contiguous int16 CUDA tensor of m elements")
+    if out is None:
+        out = torch.empty(rekey_out_bound(region.numel(), m, aux.numel()), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.device != dev:
+        raise TypeError("out must be a contiguous uint8 CUDA tensor on the region's device")
+    out_off = torch.empty(m, dtype=torch.int64, device=dev)
+    out_len = torch.empty(m, dtype=torch.int64, device=dev)
+    status = torch.empty(m, dtype=torch.int32, device=dev)
+    ws, ws_bytes = _workspace(workspace, dev)
+    ptr = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    check(lib().ambrycrc_rekey_messages_dev(ptr(region), region.numel(), ptr(msg_off), m, ptr(descs), ptr(aux),
+                                            aux.numel(), ptr(life_version), header_version, ptr(out), out.numel(),
+                                            ptr(out_off), ptr(out_len), ptr(status), ws, ws_bytes,
+                                            ctypes.c_void_p(_stream_handle(stream))),
+          "ambrycrc_rekey_messages_dev")
+    return out, out_off, out_len, status

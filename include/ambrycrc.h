@@ -303,6 +303,85 @@ int ambrycrc_transform_messages_dev(const uint8_t* d_region, uint64_t region_len
                                     uint64_t out_cap, uint64_t* d_out_off, uint64_t* d_out_len, uint32_t* d_status,
                                     void* d_ws, size_t ws_bytes, hipStream_t stream);
 
+/* ------------------------------------------------ re-keying stored PUT messages (BlobIdTransformer) */
+
+/* Status bits ambrycrc_rekey_messages_dev adds to the verify's and the transform's. */
+#define AMBRYCRC_MSG_NEEDS_CONTENT (1u << 14) /* a MetadataBlob with no replacement content supplied */
+#define AMBRYCRC_MSG_BAD_DESC      (1u << 15) /* the re-key descriptor itself is unusable (see below) */
+
+/* What the caller's StoreKeyConverter decided for one message. The bytes it refers to (the new
+ * serialized store key, a metadata blob's rewritten content) sit in one auxiliary buffer, `aux`.
+ * 40 bytes, no padding. */
+typedef struct ambrycrc_rekey_desc {
+  uint64_t key_src;         /* new serialized store key: offset in aux */
+  uint64_t content_src;     /* replacement blob content: offset in aux; UINT64_MAX = keep the stored content */
+  uint64_t content_len;
+  int64_t  props_blob_size; /* < 0: keep the stored BlobProperties.blobSize; else the value to write
+                               (compositeBlobInfo.getTotalSize(), BlobIdTransformer.java:242) */
+  uint32_t key_len;         /* 0: the converter returned no key -- message skipped (:80-82) */
+  int16_t  account_id, container_id;   /* newBlobId.getAccountId()/getContainerId() (:252) */
+} ambrycrc_rekey_desc;
+
+/* Replication's BlobIdTransformer.transform (ambry-replication/.../BlobIdTransformer.java:72-87,
+ * newMessage :159-281) for m stored messages at d_msg_off[i] in [d_region, d_region + region_len):
+ * everything ambrycrc_transform_messages_dev does, with the store key, the properties' account /
+ * container / blob size and a metadata blob's content replaced from d_desc[i] and d_aux. Per message:
+ *  - d_desc[i].key_len == 0: the converter had no key for it (:80-82). The message is skipped, as
+ *    TransformationOutput(null): status 0, out_len 0, out_off UINT64_MAX, whatever its bytes hold.
+ *  - AMBRYCRC_MSG_BAD_DESC, decided from the descriptor alone: the key span or the content span does
+ *    not lie inside [0, aux_len), or content_len > Integer.MAX_VALUE.
+ *  - the verify, exactly ambrycrc_verify_messages_dev: getMessageHeader's verifyHeader (:145), every
+ *    deserialize* CRC (:170-176), the record version and size checks; the same status bits. A message
+ *    with any of them set is not transformed.
+ *  - an update record: AMBRYCRC_MSG_NOT_PUT ("Only 'put' records are valid", :279); AMBRYCRC_MSG_BAD_RECORD
+ *    and AMBRYCRC_MSG_NOT_ENCODABLE under the transform's conditions (the same deserializers and the
+ *    same PutMessageFormatInputStream, :259-262).
+ *  - replacement content (content_src != UINT64_MAX) for a DataBlob: AMBRYCRC_MSG_BAD_DESC -- the
+ *    reference rewrites content for a MetadataBlob only (:183). A MetadataBlob (blob type 1) without
+ *    replacement content: AMBRYCRC_MSG_NEEDS_CONTENT -- the reference always rebuilds it through the
+ *    StoreKeyConverter (:185-247).
+ *    One refusal is reported per message, the first of this list that applies.
+ * Output, for status 0: PutMessageFormatInputStream's layout at header_version (1..3; V1 drops the
+ * encryption key) with life version d_life_version[i] (oldMessageInfo.getLifeVersion(), :262;
+ * nullable: the stored header's, 0 for V1/V2): the new key, the encryption-key record unchanged, the
+ * properties at BlobPropertiesSerDe VERSION_5 with account_id / container_id (:249-254) and, when
+ * props_blob_size >= 0, that blobSize (:242), the user-metadata record unchanged, and a Blob_Format_V3
+ * record with the stored blob type and compression flag over the stored content or the replacement.
+ * Every CRC is correct: the header's and the properties' are computed from the bytes written, the
+ * encryption-key and user-metadata trailers are the verified stored ones, the blob record's follows
+ * from the verified stored CRC by linearity when only its head changes (no second hash of the
+ * content), and replacement content is hashed once, from d_aux. Outputs are packed in message order
+ * into [d_out, d_out + out_cap); a message that does not fit gets AMBRYCRC_MSG_NO_ROOM and still
+ * advances the running offset, as in the transform. d_out_len[i] = 0 and d_out_off[i] = UINT64_MAX
+ * for a message not written. Bytes of d_out outside the returned spans are unspecified; when every
+ * message is refused or skipped nothing is written. d_out must not overlap the region or aux.
+ * ambrycrc_rekey_out_bound(region_len, m, aux_len) = region_len + m * AMBRYCRC_TRANSFORM_GROWTH_MAX +
+ * aux_len (saturating): an out_cap that never yields AMBRYCRC_MSG_NO_ROOM for messages that share no
+ * region bytes, provided every aux byte is used by at most one descriptor (each output is its stored
+ * message, the transform's growth, and at most its own key and content from aux).
+ * What stays with the caller, which owns the StoreKey type: the key conversion (StoreKeyConverter),
+ * a metadata blob's content rewrite -- the MetadataContentSerDe parse, the converted chunk keys and
+ * the four IllegalStateException consistency checks (:192-223) -- and the new MessageInfo with its
+ * CRC reuse (:263-276).
+ * Only enqueues on `stream`, never synchronizes; may be captured into a HIP graph with a caller
+ * workspace (d_ws >= ambrycrc_rekey_workspace_bytes(m)); d_ws NULL uses the stream's default workspace.
+ * d_aux may be NULL when aux_len is 0. */
+size_t   ambrycrc_rekey_workspace_bytes(size_t m);
+uint64_t ambrycrc_rekey_out_bound(uint64_t region_len, size_t m, uint64_t aux_len);
+int ambrycrc_rekey_messages_dev(const uint8_t* d_region, uint64_t region_len, const uint64_t* d_msg_off, size_t m,
+                                const ambrycrc_rekey_desc* d_desc, const uint8_t* d_aux, uint64_t aux_len,
+                                const int16_t* d_life_version /* nullable */, int header_version,
+                                uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off /* nullable */,
+                                uint64_t* d_out_len, uint32_t* d_status, void* d_ws, size_t ws_bytes,
+                                hipStream_t stream);
+/* The same for one message of a region in host memory (the CLMUL loop for every CRC). life_version
+ * < 0: the stored header's. out_len 0 with status 0 is the skipped message; a message longer than
+ * out_cap (or out NULL) gets AMBRYCRC_MSG_NO_ROOM. */
+int ambrycrc_rekey_message_cpu(const uint8_t* region, uint64_t region_len, uint64_t off,
+                               const ambrycrc_rekey_desc* desc, const uint8_t* aux, uint64_t aux_len,
+                               int life_version, int header_version, uint8_t* out, uint64_t out_cap,
+                               uint64_t* out_len, uint32_t* status);
+
 /* ------------------------------------------------ hard delete of stored PUT messages */
 
 /* HardDeleteRecoveryMetadata without the store key (BlobStoreHardDelete.java:204-299) plus HardDeleteInfo's
