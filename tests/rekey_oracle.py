@@ -156,11 +156,12 @@ def stored_put(key, props, um, content, hv=3, enc_key=None, life=0, bv=3, btype=
                      MF.INVALID, um_off, um_off + len(umr), life) + key + enc + pr + umr + bl
 
 
-def build_region(n=300, seed=1, corrupt_frac=0.1, big_every=17):
+def build_region(n=300, seed=1, corrupt_frac=0.1, big_every=17, max_blob=5000, max_usermeta=1200):
     """(region, offsets, is_metadata flags): headers V1/V2/V3 with and without an encryption key, properties at
     SerDe V1..V5 (a few with a non-canonical `private` byte, about 1 % with a non-ASCII string), blob records
     V1/V2/V3, about one MetadataBlob in eight, one update message in ten, corrupt_frac of the messages with one
-    flipped bit, a blob of 60-300 KB every big_every-th message and at most 5 KB otherwise."""
+    flipped bit, a blob of 60-300 KB every big_every-th message and under max_blob bytes otherwise, user
+    metadata under max_usermeta bytes."""
     rng = np.random.default_rng(seed * 7919 + 11)
     out, offs, meta = bytearray(), [], []
     for i in range(n):
@@ -177,9 +178,9 @@ def build_region(n=300, seed=1, corrupt_frac=0.1, big_every=17):
             elif (i + 1) % big_every == 0:
                 size = int(rng.integers(60000, 300000))
             else:
-                size = int(rng.integers(0, 5000))
+                size = int(rng.integers(0, max_blob))
             content = stream_bytes(seed * 100003 + i, 0, size).tobytes()
-            um = stream_bytes(seed + i, 7, int(rng.integers(0, 1200))).tobytes()
+            um = stream_bytes(seed + i, 7, int(rng.integers(0, max_usermeta))).tobytes()
             enc = stream_bytes(i, 3, int(rng.integers(1, 120))).tobytes() if (hv >= 2 and rng.integers(0, 2)) else None
             sv = int(rng.integers(1, 6))
             ctype = "application/octet" if rng.integers(0, 100) else b"caf\xc3\xa9"

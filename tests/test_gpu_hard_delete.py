@@ -171,6 +171,77 @@ def test_duplicate_offset_empty_and_single(gpu):
     assert (st, out) == HD.hard_delete(region, [put])[::2] and st == [0]
 
 
+def refused_messages(n, tag):
+    """n messages a hard delete refuses, by turns: an update message (NOT_PUT), a PUT whose blob record CRC is
+    wrong (refused by the record check), a PUT whose header CRC is wrong (refused before any record is read)."""
+    out = []
+    for i in range(n):
+        key = MF.store_key("%s-%d" % (tag, i))
+        if i % 3 == 0:
+            out.append(MF.update_message(key, version=3, kind=["ttl", "delete", "undelete"][i // 3 % 3]))
+            continue
+        size = (i * 37) % 500
+        m = bytearray(MF.put_message(key, MF.blob_properties_bytes(size), b"u" * (i % 11),
+                                     stream_bytes(3000 + i, 0, size).tobytes(), version=1 + i % 3))
+        m[-1 if i % 3 == 1 else 9] ^= 0x04
+        out.append(bytes(m))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def small_puts():
+    """1,300 clean PUTs of at most 600 B of blob, header V1/V2/V3."""
+    return [MF.put_message(MF.store_key("p%d" % i), MF.blob_properties_bytes((i * 131) % 600), b"m" * (i % 23),
+                           stream_bytes(5000 + i, 0, (i * 131) % 600).tobytes(), version=1 + i % 3)
+            for i in range(1300)]
+
+
+@pytest.mark.parametrize("where", ["start", "middle", "end"])
+@pytest.mark.parametrize("run", [40, 64, 200])
+def test_runs_of_refused_messages(gpu, run, where):
+    """A run of consecutive refused messages: two fill jobs each, of cost 0 and all at one start. hd_fill_kernel
+    reads jobs in windows of 64, the first starting at the job its share begins in, and jumps from a window of
+    empty jobs to the end of the run. Directly after a PUT with a 300 KB blob, the wave that finishes the blob
+    walks into the run: 40 messages (80 jobs) end inside its second window, which still reaches work; 64 (128
+    jobs) make that window empty and 200 (400 jobs) leave more empty windows behind it, so the jump is taken and
+    must land on the first PUT after the run. At the very start of the batch the search for a share's first job
+    must skip the run, and at the very end the run's jobs all start at the total cost."""
+    puts = small_puts()
+    bad = refused_messages(run, "r%d" % run)
+    if where == "start":
+        msgs, first = bad + puts, 0
+    elif where == "end":
+        msgs, first = puts + bad, len(puts)
+    else:
+        big = MF.put_message(MF.store_key("big"), MF.blob_properties_bytes(300_000), b"meta",
+                             stream_bytes(77, 0, 300_000).tobytes(), version=3)
+        msgs, first = puts[:650] + [big] + bad + puts[650:], 651
+    offs = [int(x) for x in np.cumsum([0] + [len(x) for x in msgs[:-1]])]
+    region = b"".join(msgs)
+    est, einfo, eout = HD.hard_delete(region, offs)
+    assert all(est[first:first + run]) and sum(1 for s in est if s) == run
+    assert len({s for s in est[first:first + run]}) == 3
+    st, info, out = run_gpu(gpu, region, offs, shift=3)
+    assert st == est
+    assert np.array_equal(info, einfo)
+    assert out == eout
+
+
+def test_every_message_refused(gpu):
+    """No message is deleted: no fill job has any cost, the region comes back byte for byte and every info entry
+    is zero."""
+    msgs = refused_messages(300, "none")
+    offs = [int(x) for x in np.cumsum([0] + [len(x) for x in msgs[:-1]])]
+    region = b"".join(msgs)
+    est, einfo, eout = HD.hard_delete(region, offs)
+    assert all(est) and eout == region
+    for plan_only in (False, True):
+        st, info, out = run_gpu(gpu, region, offs, shift=1, plan_only=plan_only)
+        assert st == est
+        assert np.array_equal(info, np.zeros(len(offs), dtype=HD.INFO)) and np.array_equal(info, einfo)
+        assert out == region
+
+
 def test_graph_capture_and_replay(gpu):
     """The call only enqueues work, so with a caller workspace it can be captured into a HIP graph (a linear
     one) and replayed on a fresh copy of the region, byte-exact."""
