@@ -13,6 +13,7 @@
 #include "put_layout.h"
 #include "record_fields.h"
 #include "rekey.h"
+#include "send.h"
 
 namespace {
 
@@ -367,6 +368,62 @@ int ambrycrc_rekey_message_cpu(const uint8_t* region, uint64_t region_len, uint6
   if (d.blob_len) memcpy(bc, (repl ? aux : region) + d.blob_src, d.blob_len);
   ambrycrc::put_be64(bc + d.blob_len, (uint64_t)ambrycrc_update(0, out + L.blob_rel, 13ull + d.blob_len));
   *out_len = L.length;
+  return AMBRYCRC_OK;
+}
+
+// MessageFormatSend.fetchDataFromReadSet for one message (MessageFormatSend.java:112-242; send.h): the
+// semantics, status and check bits of ambrycrc_send_messages_dev. ALL and BLOB run the whole verify
+// (deserializeBlobAll); the metadata flags verify the header and hash only the records they read.
+int ambrycrc_send_message_cpu(const uint8_t* region, uint64_t region_len, uint64_t off, uint64_t size, int flag,
+                              uint8_t* out, uint64_t out_cap, ambrycrc_send_info* info, uint32_t* status) {
+  if (!region || !info || !status || !ambrycrc::send_flag_ok(flag)) return AMBRYCRC_EINVAL;
+  memset(info, 0, sizeof *info);
+  info->out_off = ambrycrc::kSendNowhere;
+  const bool in_region = off <= region_len;
+  const uint64_t rem = in_region ? region_len - off : 0;
+  const uint8_t* p = region + (in_region ? off : 0);
+  const bool has_size = size != 0;
+  const bool whole_verify = flag == AMBRYCRC_SEND_ALL || flag == AMBRYCRC_SEND_BLOB;
+  ambrycrc::SendHeader H;
+  memset(&H, 0, sizeof H);
+  uint32_t hdr = AMBRYCRC_MSG_BAD_LAYOUT, hs = 0;
+  if (in_region && !(has_size && size > rem)) {
+    hdr = ambrycrc::send_header_size(p, rem, &hs);
+    if (hdr == 0 && (uint64_t)ambrycrc_update(0, p, hs - 8) != rd64(p + hs - 8)) hdr = AMBRYCRC_MSG_HEADER_CRC;
+    if (hdr == 0) hdr = ambrycrc::send_header_fields(p, rem, hs, &H);
+  }
+  // a record's CRC against its stored long
+  auto crc_bad = [&](int k) {
+    const uint8_t* q = p + H.rel[k];
+    const uint64_t span = H.rend[k] - (uint64_t)H.rel[k];
+    return (uint64_t)ambrycrc_update(0, q, span - 8) != rd64(q + span - 8);
+  };
+  const bool enc_bad = hdr == 0 && ambrycrc::send_reads_enckey(flag) && H.rel[0] != -1 && H.rel[2] == -1 && crc_bad(0);
+  ambrycrc::SendPlan s;
+  ambrycrc::send_plan(p, in_region, rem, has_size, size, flag, hdr, H, enc_bad, &s);
+  *status = s.status;
+  if (s.status) return AMBRYCRC_OK;
+  uint32_t vbits = 0;  // the verify's bits that belong in check
+  if (hdr == 0) {
+    if (whole_verify) {
+      Parsed m;
+      vbits = verify(p, rem, &m);
+    } else {
+      for (int k = 1; k <= 3; k += 2)
+        if (s.dst[k] != ambrycrc::kSendNone && crc_bad(k)) vbits |= kRecordBit[k];
+    }
+  }
+  info->rel_off = s.rel_off;
+  info->enckey_rel = s.enckey_rel;
+  info->enckey_len = s.enckey_len;
+  info->check = (vbits & ambrycrc::send_check_mask(flag)) | s.pre;
+  if (!out || s.send_len > out_cap) {
+    *status = AMBRYCRC_MSG_NO_ROOM;
+    return AMBRYCRC_OK;
+  }
+  memcpy(out, p + s.rel_off, s.send_len);
+  info->out_off = 0;
+  info->send_len = s.send_len;
   return AMBRYCRC_OK;
 }
 

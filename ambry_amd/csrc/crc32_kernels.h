@@ -375,6 +375,45 @@ struct RekeyArgs {
 hipError_t launch_rekey_plan(const RekeyArgs& a, hipStream_t s);
 hipError_t launch_rekey_write(const RekeyArgs& a, hipStream_t s);
 
+// MessageFormatSend (send_kernels.hip, ambrycrc_send.cpp; the per-message rules: send.h): the verify's
+// parse, the encryption-key records' CRCs, then one thread per message decides what is sent and what
+// each of its five verify jobs does, the spans are packed, and the verify's CRC pass copies every sent
+// record while it hashes it (SweepArgs::copy_dst).
+struct SendArgs {
+  const uint8_t* region;
+  uint64_t region_len;
+  const uint64_t* msg_off;     // [m]
+  const uint64_t* msg_size;    // [m] or null: the header's own length
+  uint64_t m;
+  int flag;                    // AMBRYCRC_SEND_*
+  uint8_t* out;
+  uint64_t out_cap;
+  ::ambrycrc_send_info* info;  // [m]; check holds send_plan's bits until send_finish_kernel
+  uint32_t* status;            // [m]
+  // the verify's parse (MsgArgs): its status and message ends (0: the header did not parse), and the
+  // 5m jobs, slot-major, which send_plan_kernel empties where a record is not to be read
+  const uint32_t* vstatus;     // [m] parse, then + the CRC pass's mismatch bits (msg_reduce_kernel)
+  const uint64_t* msg_end;     // [m]
+  uint64_t* job_off;           // [5m]
+  uint64_t* job_len;           // [5m]
+  uint32_t* expected;          // [5m]
+  const uint32_t* enc_crc;     // [m] CRCs of the slot-0 jobs (null: the flag does not read that record)
+  uint64_t* len;               // [m] span lengths, the placement scan's input
+  const uint64_t* start;       // [m + 1] their exclusive scan
+  // [5m] per job: send_plan_kernel -- the destination inside the sent span, kCopySkip (hash only; also
+  // what an emptied job gets); send_jobs_kernel -- the destination in out, or kCopySkip
+  uint64_t* copy_off;
+  // [m] each (null unless a size is given under ALL): the one plain copy of a message that goes whole
+  // without job copies, as CopyArgs (cost 0: no copy)
+  uint64_t* g_src;
+  uint64_t* g_dst;
+  uint64_t* g_len;
+  uint64_t* g_cost;
+};
+hipError_t launch_send_plan(const SendArgs& a, hipStream_t s);
+hipError_t launch_send_jobs(const SendArgs& a, hipStream_t s);
+hipError_t launch_send_finish(const SendArgs& a, hipStream_t s);
+
 // ---- copy-mode serialization of small messages by streaming the output (round 6)
 // put_stream_kernel: a wave per message writes the whole message -- header and record heads computed,
 // fields and blob gathered from their sources, trailers zero -- in 16-B output pieces (four 1 KiB wave

@@ -316,3 +316,76 @@ def rekey_dev(region, msg_off, descs, aux, header_version: int = 3, life_version
                                             ctypes.c_void_p(_stream_handle(stream))),
           "ambrycrc_rekey_messages_dev")
     return out, out_off, out_len, status
+
+
+# ------------------------------------------------------------------ serving a GET (MessageFormatSend)
+# MessageFormatFlags ordinals (AMBRYCRC_SEND_*)
+SEND_BLOB_PROPERTIES = 0
+SEND_BLOB_USER_METADATA = 1
+SEND_BLOB = 2
+SEND_ALL = 3
+SEND_BLOB_INFO = 4
+
+SEND_NOWHERE = 0xFFFFFFFFFFFFFFFF  # ambrycrc_send_info.out_off of a message not sent
+
+# numpy mirror of struct ambrycrc_send_info (32 bytes): SendInfo, the encryption key's place for
+# MessageMetadata, and the findings the reference only counts.
+SEND_INFO_DTYPE = np.dtype([("out_off", "<u8"), ("send_len", "<u8"), ("rel_off", "<u4"), ("enckey_rel", "<u4"),
+                            ("enckey_len", "<u4"), ("check", "<u4")])
+assert SEND_INFO_DTYPE.itemsize == 32
+
+
+def send_workspace_bytes(m: int) -> int:
+    return int(lib().ambrycrc_send_workspace_bytes(m))
+
+
+def send_message_cpu(region, off: int, flag: int, size=None, out_cap=None):
+    """ambrycrc_send_message_cpu: MessageFormatSend.fetchDataFromReadSet for the message at `off` of a host
+    buffer under `flag`. size: readSet.sizeInBytes, or None for the header's own message length.
+    Returns (status bits, one SEND_INFO_DTYPE record, the sent bytes; None when nothing was sent)."""
+    buf = np.frombuffer(region, dtype=np.uint8) if not isinstance(region, np.ndarray) else region
+    cap = out_cap if out_cap is not None else buf.size
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    info = np.zeros(1, dtype=SEND_INFO_DTYPE)
+    st = ctypes.c_uint32(0)
+    check(lib().ambrycrc_send_message_cpu(ctypes.c_void_p(buf.ctypes.data if buf.size else 0), buf.size, off,
+                                          0 if size is None else int(size), flag, ctypes.c_void_p(out.ctypes.data),
+                                          cap, ctypes.c_void_p(info.ctypes.data), ctypes.byref(st)),
+          "ambrycrc_send_message_cpu")
+    sent = out[:int(info[0]["send_len"])].tobytes() if st.value == 0 else None
+    return st.value, info[0].copy(), sent
+
+
+def send_messages_dev(region, msg_off, flag: int, msg_size=None, out=None, stream=None, workspace=None):
+    """ambrycrc_send_messages_dev -- MessageFormatSend.fetchDataFromReadSet for a batch of stored messages in
+    HBM under one flag: the selected spans, stored bytes verbatim, packed in message order into `out` (a
+    uint8 CUDA tensor; default: the sum of the sizes, or the region's size without sizes). msg_size: an
+    int64 CUDA tensor of readSet.sizeInBytes values, or None for each header's own length. workspace: a
+    CUDA tensor of send_workspace_bytes(m) bytes (needed to capture the call into a graph), or None.
+    Returns (out, info: a uint8 CUDA tensor holding the SEND_INFO_DTYPE array, status int32[m])."""
+    import torch
+
+    from .device import _stream_handle, _workspace
+
+    if region.dtype != torch.uint8 or not region.is_cuda:
+        raise TypeError("region must be a uint8 CUDA tensor")
+    dev = region.device
+    if msg_off.dtype != torch.int64 or not msg_off.is_cuda or not msg_off.is_contiguous() or msg_off.device != dev:
+        raise TypeError("msg_off must be a contiguous int64 CUDA tensor on the region's device")
+    m = msg_off.numel()
+    if msg_size is not None and (msg_size.dtype != torch.int64 or not msg_size.is_cuda or msg_size.device != dev
+                                 or not msg_size.is_contiguous() or msg_size.numel() != m):
+        raise TypeError("msg_size must be a contiguous int64 CUDA tensor of m elements on the region's device")
+    if out is None:
+        out = torch.empty(max(region.numel(), 1), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.device != dev:
+        raise TypeError("out must be a contiguous uint8 CUDA tensor on the region's device")
+    info = torch.empty(m * SEND_INFO_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    status = torch.empty(m, dtype=torch.int32, device=dev)
+    ws, ws_bytes = _workspace(workspace, dev)
+    ptr = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    check(lib().ambrycrc_send_messages_dev(ptr(region), region.numel(), ptr(msg_off), ptr(msg_size), m, flag,
+                                           ptr(out), out.numel(), ptr(info), ptr(status), ws, ws_bytes,
+                                           ctypes.c_void_p(_stream_handle(stream))),
+          "ambrycrc_send_messages_dev")
+    return out, info, status

@@ -441,6 +441,79 @@ int ambrycrc_hard_delete_message_cpu(uint8_t* region, uint64_t region_len, uint6
                                      const ambrycrc_hard_delete_info* recovery /* nullable */, int plan_only,
                                      uint32_t* status, ambrycrc_hard_delete_info* info /* nullable */);
 
+/* ------------------------------------------------ serving a GET from stored messages (MessageFormatSend) */
+
+/* MessageFormatFlags ordinals (ambry-api/.../MessageFormatFlags.java:20). */
+#define AMBRYCRC_SEND_BLOB_PROPERTIES 0
+#define AMBRYCRC_SEND_BLOB_USER_METADATA 1
+#define AMBRYCRC_SEND_BLOB 2
+#define AMBRYCRC_SEND_ALL 3
+#define AMBRYCRC_SEND_BLOB_INFO 4
+
+typedef struct ambrycrc_send_info {   /* 32 bytes, no padding */
+  uint64_t out_off;     /* where the span went in d_out; UINT64_MAX when nothing was sent */
+  uint64_t send_len;    /* SendInfo.sizetoSend(); 0 when nothing was sent */
+  uint32_t rel_off;     /* SendInfo.relativeOffset() */
+  uint32_t enckey_rel;  /* the key bytes inside BlobEncryptionKey_Format_V1 (record offset + 6),
+                           relative to the message; 0 = MessageMetadata null */
+  uint32_t enckey_len;
+  uint32_t check;       /* AMBRYCRC_MSG_* findings that the reference only counts, or never looks for */
+} ambrycrc_send_info;
+
+/* MessageFormatSend.fetchDataFromReadSet (ambry-messageformat/.../MessageFormatSend.java:112-242) for m
+ * stored messages at d_msg_off[i] in [d_region, d_region + region_len) under one MessageFormatFlags value:
+ * what to send of each message, the checks the reference runs on the way, and the response body -- the
+ * selected spans, stored bytes verbatim (wrong trailers included), packed in message order into
+ * [d_out, d_out + out_cap) over the sent messages only. d_msg_size[i] is readSet.sizeInBytes(i); NULL: each
+ * header's own message length (an unparseable header is then fatal under ALL too).
+ *   flag                 rel_off                  send_len                               reference
+ *   ALL                  0                        size                                   :142
+ *   BLOB                 blob record              blob record size                       :160-161
+ *   BLOB_PROPERTIES      properties record        properties record size                 :177-178
+ *   BLOB_USER_METADATA   user-metadata record     user-metadata record size              :191-192
+ *   BLOB_INFO            properties record        properties + user-metadata sizes       :204-205
+ * d_status[i]: what makes the reference throw out of fetchDataFromReadSet; nothing is sent for such a
+ * message (send_len 0, out_off UINT64_MAX, the other info fields 0, no byte of d_out). In this order:
+ *  - AMBRYCRC_MSG_BAD_LAYOUT: the offset or off + size lies past the region, or the size is 0;
+ *  - the header, as ambrycrc_verify_messages_dev: AMBRYCRC_MSG_BAD_VERSION / _HEADER_CRC, or _BAD_LAYOUT
+ *    for checkHeaderConstraints, which verifyHeader runs (MessageFormatRecord.java:1132-1145;
+ *    parseHeaderAndVerifyStoreKey, MessageFormatSend.java:247-277). Not under ALL with a size given: the
+ *    reference never parses the header for that send, and the message goes whole;
+ *  - AMBRYCRC_MSG_NOT_PUT: an update message under any flag but ALL. Deviation: its record offsets are -1
+ *    in the reference, which then sends or reads at negative offsets -- an accident, refused here;
+ *  - AMBRYCRC_MSG_BAD_LAYOUT: the sent span, or the encryption-key record where it is read, does not lie
+ *    inside [0, size);
+ *  - the encryption-key record of a V2 / V3 header, under BLOB, BLOB_USER_METADATA and BLOB_INFO, where
+ *    deserializeBlobEncryptionKey throws (:150-158, :188-203, :288-295): AMBRYCRC_MSG_ENCKEY_CRC, or the
+ *    record's own _BAD_VERSION / _BAD_RECORD. BLOB_PROPERTIES never reads that record, nor does ALL;
+ *  - AMBRYCRC_MSG_NO_ROOM: the span does not fit below out_cap. The running offset still advances, as in
+ *    the transform; rel_off, the encryption-key fields and check are still reported. With out_cap >= the
+ *    sum of the sizes no message gets it.
+ * The store-key comparison (:270-275) stays with the caller, as everywhere else.
+ * d_info[i].check: what the reference counts and carries on from, or does not look at (0 for a refused
+ * message). ALL and BLOB: exactly the bits ambrycrc_verify_messages_dev gives the message
+ * (deserializeBlobAll, :131-139), plus AMBRYCRC_MSG_NOT_PUT for an update message; under ALL with a size
+ * that differs from the header's message length the given bytes are sent and AMBRYCRC_MSG_BAD_LAYOUT is
+ * added when the size is the shorter one. The three metadata flags: the CRC bit and the record-check bits
+ * (_BAD_VERSION / _BAD_RECORD) of the records that were sent, which the reference leaves to the router.
+ * Records the flag does not send and the reference does not read are not read here either: a BLOB_INFO
+ * batch touches headers, keys, encryption-key, properties and user-metadata records, and the first and
+ * last bytes of each blob record (the parse's), never a blob's content.
+ * Every sent record is read once, hashed and copied by the same pass. The same offset may be listed twice
+ * and messages may overlap (the region is only read); d_out must not overlap the region.
+ * Only enqueues on `stream`, never synchronizes; may be captured into a HIP graph with a caller workspace
+ * (d_ws >= ambrycrc_send_workspace_bytes(m)); d_ws NULL uses the stream's default workspace. */
+size_t ambrycrc_send_workspace_bytes(size_t m);
+int ambrycrc_send_messages_dev(const uint8_t* d_region, uint64_t region_len, const uint64_t* d_msg_off,
+                               const uint64_t* d_msg_size /* nullable */, size_t m, int flag,
+                               uint8_t* d_out, uint64_t out_cap, ambrycrc_send_info* d_info,
+                               uint32_t* d_status, void* d_ws, size_t ws_bytes, hipStream_t stream);
+/* The same for one message of a region in host memory (the CLMUL loop, memcpy). size 0: the header's own
+ * message length (so a size of 0 cannot be passed here; the batch refuses it). A sent span starts at out
+ * (info->out_off 0); out NULL or send_len > out_cap: AMBRYCRC_MSG_NO_ROOM. */
+int ambrycrc_send_message_cpu(const uint8_t* region, uint64_t region_len, uint64_t off, uint64_t size /* 0: the header's */,
+                              int flag, uint8_t* out, uint64_t out_cap, ambrycrc_send_info* info, uint32_t* status);
+
 /* ------------------------------------- CRC-trailered records (store files, headers) */
 
 /* Item i = [off[i], off[i] + len[i]) ends in the big-endian 8-B CRC (a long, high word zero)
