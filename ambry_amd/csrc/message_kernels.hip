@@ -678,6 +678,7 @@ __global__ __launch_bounds__(256) void region_long_kernel(MsgArgs a, RegionArgs 
     const uint32_t p = q - lr.piece0, np = lr.pieces;
     if (p >= np) continue;  // a record listed empty
     const uint64_t s = (uint64_t)p * kLongPiece, e = min((uint64_t)lr.len, s + kLongPiece);
+    // (a last piece of 1..3 bytes, of a record of 65536 k + 1..3 bytes, is hashed from its bytes there)
     const uint32_t c = region::record_crc_runs_wave(region::TabC{tbl}, nib, dn, g.base, rk, lr.pa + s, e - s, lane);
     if (lane == 0) g.lng.slot[q] = c;
     __threadfence();  // the slot before the count

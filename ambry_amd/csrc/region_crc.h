@@ -391,7 +391,7 @@ __device__ __forceinline__ void stage_direct_nib(uint32_t* __restrict__ dn, cons
 }
 
 // zlib CRC-32 of a long record by the whole wave from the run sums (every lane the same pa, len;
-// len >= 4): the record's runs [A0, B1) as record_crc takes them (head and tail runs from the
+// under four bytes: bytewise in every lane): the record's runs [A0, B1) as record_crc takes them (head and tail runs from the
 // bytes, the interior from rk), in rounds of 256 aligned to the record's last run -- lane l takes
 // runs 4l .. 4l + 3 of a round (one 16-B load of sums, folded by x^(8*64)) -- four streams of rounds
 // folded by x^(8*65536), combined by x^(8*16384), the lanes merged by the tree over 256-B slices
@@ -404,7 +404,15 @@ __device__ __forceinline__ uint32_t record_crc_runs_wave(const Tab& t, const uin
                                                          const uint8_t* __restrict__ base,
                                                          const uint32_t* __restrict__ rk, uint64_t pa, uint64_t len,
                                                          uint32_t lane) {
+  // Under four bytes (wave-uniform: region_long_kernel's last piece of a record of 65536 k + 1..3 bytes) from
+  // the bytes, as in record_crc: below, the rest of the initial register is added at the head run's end, which
+  // is the register's place only when the record goes on into the next run.
   const uint64_t pb = pa + len;
+  if (len < 4) {
+    uint32_t c = 0xFFFFFFFFu;
+    for (uint64_t i = pa; i < pb; ++i) c = t.t0((c ^ base[i]) & 0xffu) ^ (c >> 8);
+    return len ? ~c : 0u;
+  }
   const uint64_t A0 = pa & ~uint64_t(63), B1 = (pb + 63) & ~uint64_t(63);
   const int64_t n = (int64_t)((B1 - A0) >> 6), k0 = (int64_t)(A0 >> 6);
   const int lo = (int)(pa - A0), hi = pb - A0 < 64 ? (int)(pb - A0) : 64;

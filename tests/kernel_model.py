@@ -587,7 +587,11 @@ class RegionModel:
         """region_crc.h record_crc_runs_wave: a long record by the whole wave from the run sums --
         the record's runs [A0, B1) (head and tail runs from the bytes, as job_crc), run
         n - 64(V - v) + l in lane l of round v, folded over rounds by x^(8*4096) (POW[12]), merged by
-        the tree over 256-B lane slices (POW[8 + k]), lane 63 ending at B1, then the x^(-8d) un-shift."""
+        the tree over 256-B lane slices (POW[8 + k]), lane 63 ending at B1, then the x^(-8d) un-shift. Under
+        four bytes: bytewise, as job_crc (the rest of the initial register, added at the head run's end below,
+        belongs there only when the record goes on into the next run)."""
+        if ln < 4:
+            return self.job_crc(mem, reg0, rk, off, ln)
         nruns = len(rk)
         buf = bytes(reg0) + mem + bytes(nruns * 64 - reg0 - len(mem))
         pa = reg0 + off
@@ -620,6 +624,15 @@ class RegionModel:
             if d & (1 << k):
                 x = self.inv(x, k)
         return x ^ 0xFFFFFFFF
+
+    def long_crc(self, mem: bytes, reg0: int, rk, off: int, ln: int) -> int:
+        """message_kernels.hip region_long_kernel: a long record as 64 KiB pieces from its start, each piece's
+        CRC by the whole wave from the run sums (job_crc_wave, which takes a last piece under four bytes from
+        its bytes), folded by long_fold."""
+        P = 64 << 10
+        sl = [self.job_crc_wave(mem, reg0, rk, off + s, min(P, ln - s)) for s in range(0, ln, P)]
+        return self.long_fold(sl, ln - (len(sl) - 1) * P)
+
 
 def snap_cut(cs: int, ln: int, r: int) -> int:
     a = (cs + r + 15) & ~15

@@ -190,3 +190,22 @@ def test_long_fold_model_matches_zlib(ambry):
         sl = [zlib.crc32(mem[i:i + P]) for i in range(0, ln, P)]
         assert len(sl) == npieces
         assert rm.long_fold(sl, last) == zlib.crc32(mem), (npieces, last)
+
+
+def test_long_record_pieces_model_matches_zlib(ambry):
+    """region_long_kernel's split of a long record into 64 KiB pieces from its start, each piece by
+    record_crc_runs_wave from the run sums, against zlib: last pieces of 1 to 4 bytes (under four the wave
+    form's algebra does not apply -- it adds the rest of the initial register at the run end -- and it hashes
+    the piece from its bytes), a few bytes and a full piece, ending on and off the run grid."""
+    import zlib
+
+    from kernel_model import RegionModel, table_image
+
+    rm = RegionModel(table_image())
+    P = 64 << 10
+    mem = stream_bytes(4444, 0, 2 * P + 200).tobytes()
+    for reg0 in (0, 37):
+        rk = rm.runs(mem, reg0)
+        for a, ln in ((0, P + 1), (5, P + 2), (64 - reg0, P + 3), (63, P + 1), (61, P + 3), (9, P + 4), (1, P + 77),
+                      (3, 2 * P), (100, 2 * P - 1)):
+            assert rm.long_crc(mem, reg0, rk, a, ln) == zlib.crc32(mem[a:a + ln]), (reg0, a, ln)
