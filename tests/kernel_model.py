@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import bisect
 import ctypes
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -646,3 +647,108 @@ def gf2_mul(a: int, b: int) -> int:
             p ^= b
         b = (b >> 1) ^ (0xEDB88320 if b & 1 else 0)
     return p
+
+
+# ---------------------------------------------------------------- put_stream_kernel's partition of a message
+# crc32_kernels.hip: a streamed message's output is cut into 16-B pieces on the destination's 16-B grid
+# (mis = m0 & 15; piece t of the two super-blocks starts at message-relative dd = (S0 - m0) + 16 t, S0 = m0
+# rounded down to 64). stream_piece_src stores a piece that lies wholly inside one data segment with one 16-B
+# store; every other segment byte goes through the segment's 32 edge slots, one byte store each. The functions
+# take arrays with a leading batch shape, so a test can run them over many messages at once.
+STREAM_PIECES = 2 * 4 * 64  # kStreamSbs super-blocks x 4 wave pieces x 64 lanes
+
+
+def stream_edge_slots(mis, lo, hi):
+    """(e, live), shape lo.shape + (32,): slot j < 16 of the segment [lo, hi) is byte lo + j, live below
+    min(up, hi); slot j >= 16 is byte max(up, dn) + j - 16, live below hi. up: the first piece boundary at or
+    above lo, dn: the last at or below hi, both on the destination's grid."""
+    mis, lo, hi = (np.asarray(v, dtype=np.int64)[..., None] for v in (mis, lo, hi))
+    j = np.arange(32, dtype=np.int64)
+    up = ((lo + mis + 15) & ~15) - mis
+    dn = ((hi + mis) & ~15) - mis
+    e = np.where(j < 16, lo + j, np.maximum(up, dn) + j - 16)
+    live = np.where(j < 16, e < np.minimum(up, hi), e < hi)
+    return e, live
+
+
+def stream_piece_segment(los, his, dd):
+    """stream_piece_src: the segment that holds the whole piece [dd, dd + 16), or -1. los, his: [..., 5], dd:
+    [..., P]. The candidate is the last segment whose lo <= dd (segments in message order, lo nondecreasing)."""
+    los, his, dd = np.asarray(los, dtype=np.int64), np.asarray(his, dtype=np.int64), np.asarray(dd, dtype=np.int64)
+    k = sum((dd >= los[..., i:i + 1]).astype(np.int64) for i in range(1, 5))
+    lo_k = np.take_along_axis(los, k, axis=-1)
+    hi_k = np.take_along_axis(his, k, axis=-1)
+    return np.where((dd >= lo_k) & (dd + 16 <= hi_k), k, -1)
+
+
+def stream_store_counts(m0, los, his, width, pad=64):
+    """How often the kernel's source stores write each byte: (count, owner), both [N, pad + width]; column
+    pad + x is message byte x (x from -pad: a store below the message would show). owner: the segment of the
+    last store to the byte (-1: none). m0: [N] the messages' starts from a 64-aligned base; los, his: [N, 5]."""
+    m0, los, his = (np.asarray(v, dtype=np.int64) for v in (m0, los, his))
+    n = len(m0)
+    count = np.zeros((n, pad + width), dtype=np.int32)
+    owner = np.full((n, pad + width), -1, dtype=np.int8)
+    mis = m0 & 15
+    dd = ((m0 & ~63) - m0)[:, None] + 16 * np.arange(STREAM_PIECES, dtype=np.int64)
+    seg = stream_piece_segment(los, his, dd)
+    rows, cols = np.nonzero(seg >= 0)
+    for b in range(16):
+        np.add.at(count, (rows, pad + dd[rows, cols] + b), 1)
+        owner[rows, pad + dd[rows, cols] + b] = seg[rows, cols]
+    for s in range(5):
+        e, live = stream_edge_slots(mis, los[:, s], his[:, s])
+        rows, cols = np.nonzero(live)
+        np.add.at(count, (rows, pad + e[rows, cols]), 1)
+        owner[rows, pad + e[rows, cols]] = s
+    return count, owner
+
+
+# ---------------------------------------------------------------- gather_copy_kernel's copy_range
+def align_byte(hi: int, lo: int, r: int) -> int:
+    """v_alignbyte_b32: bytes r .. r + 3 of the 8-byte value hi:lo."""
+    return (((hi << 32) | lo) >> (8 * r)) & 0xFFFFFFFF
+
+
+def shift_pair(a, b, q: int, r: int):
+    """put_kernels.hip shift_pair<Q>: dwords of bytes [4Q + r, 4Q + r + 16) of a || b (four dwords each)."""
+    w = list(a) + list(b)
+    if r == 0:
+        return w[q:q + 4]
+    return [align_byte(w[q + k + 1], w[q + k], r) for k in range(4)]
+
+
+def copy_range_model(dst: int, src: int, n: int, mem=None):
+    """put_kernels.hip copy_range for one wave: head (dst, src, count) of bytewise lanes, pieces [(dst address,
+    first aligned load address, second aligned load address or None)], tail (dst, src, count), and `loads`,
+    every 16-B source block a piece reads. With mem (bytes, addresses index it) also `out`, {dst address:
+    byte}, the pieces' bytes built by shift_pair from the two loads."""
+    head0 = (16 - (dst & 15)) & 15
+    head = min(head0, n)
+    body = n - head
+    n16 = body >> 4
+    d1, s1 = dst + head, src + head
+    shift = s1 & 15
+    s0 = s1 - shift
+    pieces, loads, out = [], [], {}
+    for p in range(n16):
+        la = s0 + 16 * p
+        lb = la + 16 if shift else None
+        pieces.append((d1 + 16 * p, la, lb))
+        loads.append(la)
+        if lb is not None:
+            loads.append(lb)
+        if mem is not None:
+            a = [int.from_bytes(mem[la + 4 * k:la + 4 * k + 4], "little") for k in range(4)]
+            b = [int.from_bytes(mem[lb + 4 * k:lb + 4 * k + 4], "little") for k in range(4)] if shift else [0] * 4
+            for k, w in enumerate(shift_pair(a, b, shift >> 2, shift & 3)):
+                for t in range(4):
+                    out[d1 + 16 * p + 4 * k + t] = (w >> (8 * t)) & 0xFF
+    t = body & 15
+    if mem is not None:
+        for i in range(head):
+            out[dst + i] = mem[src + i]
+        for i in range(t):
+            out[d1 + 16 * n16 + i] = mem[s1 + 16 * n16 + i]
+    return SimpleNamespace(head=(dst, src, head), pieces=pieces, tail=(d1 + 16 * n16, s1 + 16 * n16, t), loads=loads,
+                           out=out, shift=shift, n16=n16)

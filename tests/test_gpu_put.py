@@ -2,7 +2,11 @@
 CRC trailer filled, byte-exact against oracle/message_format.py's layouts (zlib CRCs), then
 verified by ambrycrc_verify_messages_dev (round trip). Copy mode (fields and blobs gathered from
 their own buffers, at any alignment) and in-place mode (bytes already at ambrycrc_put_layout's
-offsets); batches under and over the group-phase threshold; 4 MiB blobs."""
+offsets); batches under and over the group-phase threshold; 4 MiB blobs.
+
+These batches are random: which destination phase, source residue and length a field gets is chance. The cells
+of the write-side kernels' case split are covered by construction in put_lattice.py (test_put_lattice.py asserts
+the coverage, test_gpu_put_geometry.py runs it)."""
 import numpy as np
 import pytest
 
