@@ -103,6 +103,17 @@ _SIGNATURES = [
     ("ambrycrc_send_message_cpu", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p,
       ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
+    ("ambrycrc_chain_workspace_bytes", ctypes.c_size_t, [ctypes.c_uint64, ctypes.c_size_t]),
+    ("ambrycrc_chain_messages_dev", ctypes.c_int,
+     [_u8p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t, _u8p, _u8p, ctypes.c_void_p, ctypes.c_size_t,
+      ctypes.c_void_p]),
+    ("ambrycrc_recover_workspace_bytes", ctypes.c_size_t, [ctypes.c_uint64, ctypes.c_size_t]),
+    ("ambrycrc_recover_messages_dev", ctypes.c_int,
+     [_u8p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t, _u8p, _u8p, _u8p, _u8p, ctypes.c_void_p,
+      ctypes.c_size_t, ctypes.c_void_p]),
+    ("ambrycrc_recover_messages_cpu", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p]),
     ("ambrycrc_hard_delete_workspace_bytes", ctypes.c_size_t, [ctypes.c_size_t]),
     ("ambrycrc_hard_delete_messages_dev", ctypes.c_int,
      [_u8p, ctypes.c_uint64, _u8p, ctypes.c_size_t, _u8p, ctypes.c_int, _u8p, _u8p, ctypes.c_void_p, ctypes.c_size_t,

@@ -12,6 +12,7 @@
 #include "hard_delete.h"
 #include "put_layout.h"
 #include "record_fields.h"
+#include "recover.h"
 #include "rekey.h"
 #include "send.h"
 
@@ -300,6 +301,55 @@ int ambrycrc_verify_message_cpu(const uint8_t* region, uint64_t region_len, uint
   Parsed m;
   *status = off <= region_len ? verify(region + off, region_len - off, &m) : (uint32_t)AMBRYCRC_MSG_BAD_LAYOUT;
   if (msg_end) *msg_end = off <= region_len && m.end ? off + m.end : 0;
+  return AMBRYCRC_OK;
+}
+
+// BlobStoreRecovery.recover (BlobStoreRecovery.java:43-139) as the plain sequential loop: the chain's
+// acceptance test (recover.h), the verify above, the shared field reader (record_fields.h).
+int ambrycrc_recover_messages_cpu(const uint8_t* region, uint64_t region_len, uint64_t start, size_t max_m,
+                                  uint64_t* msg_off, ambrycrc_message_info* info, uint32_t* status,
+                                  ambrycrc_recover_result* result) {
+  if ((!region && region_len) || !msg_off || !result || start > region_len || max_m == 0 || max_m >= (1ull << 31))
+    return AMBRYCRC_EINVAL;
+  const auto crc = [](const uint8_t* p, uint32_t n) { return ambrycrc_update(0, p, n); };
+  ambrycrc_recover_result r;
+  memset(&r, 0, sizeof r);
+  uint64_t off = start, first_bad = max_m;
+  uint32_t bad_status = 0;
+  while (off < region_len && r.chained < max_m) {
+    uint64_t next = 0;
+    r.end_status = ambrycrc::chain_header(region + off, region_len - off, crc, &next);
+    if (r.end_status) break;
+    const size_t i = (size_t)r.chained++;
+    msg_off[i] = off;
+    Parsed m;
+    uint32_t st = verify(region + off, region_len - off, &m);
+    ambrycrc_message_info o;
+    memset(&o, 0, sizeof o);
+    if (st == 0) st = ambrycrc::message_info_fields(region + off, off, &o);
+    if (info) info[i] = o;
+    if (status) status[i] = st;
+    if (st && first_bad == max_m) {
+      first_bad = i;
+      bad_status = st;
+    }
+    off += next;
+  }
+  for (size_t i = (size_t)r.chained; i < max_m; ++i) {
+    msg_off[i] = ~0ull;
+    if (info) memset(&info[i], 0, sizeof info[i]);
+    if (status) status[i] = AMBRYCRC_MSG_BAD_LAYOUT;
+  }
+  r.recovered = r.chained;
+  r.end_off = off;
+  r.more = r.end_status == 0 && off != region_len ? 1u : 0u;
+  if (first_bad != max_m) {
+    r.recovered = first_bad;
+    r.end_off = msg_off[first_bad];
+    r.end_status = bad_status;
+    r.more = 0;
+  }
+  *result = r;
   return AMBRYCRC_OK;
 }
 

@@ -19,12 +19,6 @@
 
 namespace ambrycrc {
 
-__host__ __device__ inline uint64_t ld_be64(const uint8_t* p) {
-  uint64_t v;
-  __builtin_memcpy(&v, p, 8);
-  return __builtin_bswap64(v);
-}
-
 constexpr uint64_t kRekeyKeep = ~0ull;       // ambrycrc_rekey_desc::content_src: keep the stored content
 constexpr uint32_t kSerdeBlobSize = 19;      // offset of blobSize in the SerDe bytes (version, ttl, private, creationTime)
 

@@ -317,9 +317,27 @@ def _hard_delete_info_dtype():
     return globals()["HARD_DELETE_INFO"]
 
 
+def _recover_dtypes():
+    """struct ambrycrc_message_info (48 bytes) and struct ambrycrc_recover_result (32 bytes) of include/ambrycrc.h
+    as numpy structured dtypes, built on first use and kept as MESSAGE_INFO and RECOVER_RESULT."""
+    if "MESSAGE_INFO" not in globals():
+        import numpy as np
+
+        info = np.dtype([("msg_off", "<u8"), ("size", "<u8"), ("expires_at_ms", "<i8"), ("operation_time_ms", "<i8"),
+                         ("key_rel", "<u4"), ("key_len", "<u4"), ("account_id", "<i2"), ("container_id", "<i2"),
+                         ("life_version", "<i2"), ("flags", "u1"), ("header_version", "u1")])
+        res = np.dtype([("chained", "<u8"), ("recovered", "<u8"), ("end_off", "<u8"), ("end_status", "<u4"),
+                        ("more", "<u4")])
+        assert info.itemsize == 48 and res.itemsize == 32
+        globals()["MESSAGE_INFO"], globals()["RECOVER_RESULT"] = info, res
+    return globals()["MESSAGE_INFO"], globals()["RECOVER_RESULT"]
+
+
 def __getattr__(name):
     if name == "HARD_DELETE_INFO":
         return _hard_delete_info_dtype()
+    if name in ("MESSAGE_INFO", "RECOVER_RESULT"):
+        return _recover_dtypes()[name == "RECOVER_RESULT"]
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -447,6 +465,97 @@ def chain_messages_host(region: bytes, start: int = 0, max_messages: int = 1 << 
     n = lib().ambrycrc_chain_messages_host(ctypes.c_void_p(arr.ctypes.data if arr.nbytes else 0), arr.nbytes, start,
                                            offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), max_messages)
     return [int(x) for x in offs[:n]]
+
+
+# ------------------------------------------------ log-region recovery on the device
+
+MSG_BAD_INFO = 1 << 16    # AMBRYCRC_MSG_BAD_INFO: an operation time below -1 (MessageInfo's constructor throws)
+NO_MESSAGE = (1 << 64) - 1  # d_msg_off of a slot past the chain (UINT64_MAX; -1 in the int64 tensor)
+
+
+def chain_workspace_bytes(region_len: int, max_messages: int) -> int:
+    """Bytes of caller workspace ambrycrc_chain_messages_dev needs."""
+    return lib().ambrycrc_chain_workspace_bytes(region_len, max_messages)
+
+
+def recover_workspace_bytes(region_len: int, max_messages: int) -> int:
+    """Bytes of caller workspace ambrycrc_recover_messages_dev needs."""
+    return lib().ambrycrc_recover_workspace_bytes(region_len, max_messages)
+
+
+def _check_region(region):
+    torch = _torch()
+    if region.dtype != torch.uint8 or not region.is_cuda or not region.is_contiguous():
+        raise TypeError("region must be a contiguous uint8 CUDA tensor")
+
+
+def chain_messages(region, start: int = 0, max_messages: int = 1 << 20, stream=None, workspace=None, out=None):
+    """The message chain of a log region in HBM, found on the GPU (ambrycrc_chain_messages_dev): no host
+    synchronisation. out: (msg_off, result) of an earlier call, to write into (a captured graph's outputs).
+
+    Returns (msg_off int64[max_messages] CUDA tensor: the starts in log order, then -1 (UINT64_MAX);
+    result uint8[32] CUDA tensor: one RECOVER_RESULT record -- recover_result(result) reads it)."""
+    torch = _torch()
+    _check_region(region)
+    msg_off, result = out if out is not None else (
+        torch.empty(max_messages, dtype=torch.int64, device=region.device),
+        torch.empty(32, dtype=torch.uint8, device=region.device))
+    ws, ws_bytes = _workspace(workspace, region.device)
+    check(lib().ambrycrc_chain_messages_dev(_ptr(region), region.numel(), start, max_messages, _ptr(msg_off),
+                                            _ptr(result), ws, ws_bytes, ctypes.c_void_p(_stream_handle(stream))),
+          "ambrycrc_chain_messages_dev")
+    return msg_off, result
+
+
+def recover_messages(region, start: int = 0, max_messages: int = 1 << 20, stream=None, workspace=None, out=None):
+    """BlobStoreRecovery.recover over region[start:] on the GPU (ambrycrc_recover_messages_dev): the chain, the
+    verify of every chained message, the MessageInfo fields. No host synchronisation. out: the four tensors of
+    an earlier call, to write into.
+
+    Returns (msg_off int64[max_messages], info uint8[max_messages, 48]: rows of MESSAGE_INFO, zero unless the
+    status is 0; status int32[max_messages]; result uint8[32]: one RECOVER_RESULT record), CUDA tensors."""
+    torch = _torch()
+    _check_region(region)
+    msg_off, info, status, result = out if out is not None else (
+        torch.empty(max_messages, dtype=torch.int64, device=region.device),
+        torch.empty((max_messages, 48), dtype=torch.uint8, device=region.device),
+        torch.empty(max_messages, dtype=torch.int32, device=region.device),
+        torch.empty(32, dtype=torch.uint8, device=region.device))
+    ws, ws_bytes = _workspace(workspace, region.device)
+    check(lib().ambrycrc_recover_messages_dev(_ptr(region), region.numel(), start, max_messages, _ptr(msg_off),
+                                              _ptr(info), _ptr(status), _ptr(result), ws, ws_bytes,
+                                              ctypes.c_void_p(_stream_handle(stream))),
+          "ambrycrc_recover_messages_dev")
+    return msg_off, info, status, result
+
+
+def recover_result(result):
+    """The RECOVER_RESULT record of a result tensor (copies it to the host: synchronises)."""
+    import numpy as np
+
+    return np.frombuffer(result.cpu().numpy().tobytes(), dtype=_recover_dtypes()[1])[0]
+
+
+def recover_messages_cpu(region, start: int = 0, max_messages: int = 1 << 20):
+    """ambrycrc_recover_messages_cpu: the same over a region in host memory (bytes-like or numpy uint8).
+    Returns (msg_off uint64[max_messages], info MESSAGE_INFO[max_messages], status uint32[max_messages],
+    result: a RECOVER_RESULT record), numpy."""
+    import numpy as np
+
+    info_dt, res_dt = _recover_dtypes()
+    arr = np.frombuffer(region, dtype=np.uint8) if isinstance(region, (bytes, bytearray, memoryview)) else \
+        np.ascontiguousarray(region, dtype=np.uint8)
+    n = int(max_messages) if 0 < max_messages < (1 << 31) else 0  # (the entry refuses the others)
+    msg_off = np.zeros(n, dtype=np.uint64)
+    info = np.zeros(n, dtype=info_dt)
+    status = np.zeros(n, dtype=np.uint32)
+    res = np.zeros(1, dtype=res_dt)
+    check(lib().ambrycrc_recover_messages_cpu(ctypes.c_void_p(arr.ctypes.data if arr.nbytes else 0), arr.nbytes,
+                                              start, max_messages, ctypes.c_void_p(msg_off.ctypes.data),
+                                              ctypes.c_void_p(info.ctypes.data), ctypes.c_void_p(status.ctypes.data),
+                                              ctypes.c_void_p(res.ctypes.data)),
+          "ambrycrc_recover_messages_cpu")
+    return msg_off, info, status, res[0]
 
 
 # ------------------------------------------------ multi-GPU batch + RCCL all-gather (§8e)

@@ -514,6 +514,81 @@ int ambrycrc_send_messages_dev(const uint8_t* d_region, uint64_t region_len, con
 int ambrycrc_send_message_cpu(const uint8_t* region, uint64_t region_len, uint64_t off, uint64_t size /* 0: the header's */,
                               int flag, uint8_t* out, uint64_t out_cap, ambrycrc_send_info* info, uint32_t* status);
 
+/* ------------------------------------- log-region recovery: message chain and MessageInfo */
+
+/* Status bit the recover entries add to the verify bits: a verified message whose operation time (a PUT's
+ * creation time, an update's time) is below -1, for which `new MessageInfo(...)` throws
+ * IllegalArgumentException (MessageInfo.java:172) and BlobStoreRecovery.recover stops with
+ * LogFileFormatError. */
+#define AMBRYCRC_MSG_BAD_INFO (1u << 16)
+
+/* What BlobStoreRecovery.recover builds for one message (BlobStoreRecovery.java:75-116), but for the
+ * store key, whose bytes are named by key_rel / key_len (the store-key factory stays with the caller).
+ * 48 bytes, no padding. */
+typedef struct ambrycrc_message_info {
+  uint64_t msg_off;            /* message start in the region */
+  uint64_t size;               /* header + key + message size: MessageInfo.getSize() */
+  int64_t  expires_at_ms;      /* -1 = Utils.Infinite_Time; a PUT's Utils.addSecondsToEpochTime(creation, ttl)
+                                  (Utils.java:1036-1041: -1 if either is -1, TimeUnit.SECONDS.toMillis's
+                                  saturation, Java's wrapping add); -1 for every update (MessageInfo.java:104-108) */
+  int64_t  operation_time_ms;  /* PUT: creation time; update: the record's time (-1 at Update_Format_V1) */
+  uint32_t key_rel, key_len;   /* the store key's bytes: header size, first record offset - header size */
+  int16_t  account_id, container_id, life_version; /* -1, -1 at BlobPropertiesSerDe V1 and Update_Format_V1;
+                                                      life_version: the header's at V3, else 0 */
+  uint8_t  flags;              /* bit0 deleted, bit1 ttlUpdated, bit2 undeleted; 0 for a PUT */
+  uint8_t  header_version;
+} ambrycrc_message_info;
+
+typedef struct ambrycrc_recover_result { /* 32 bytes */
+  uint64_t chained;     /* messages the chain found (<= max_m) */
+  uint64_t recovered;   /* leading messages with status 0 (recover only; = chained for the chain entry) */
+  uint64_t end_off;     /* RecoveryResult.currentStartOffset, region-relative */
+  uint32_t end_status;  /* 0: reached region_len, or stopped for max_m (more = 1); else why it stopped */
+  uint32_t more;        /* 1: stopped only because max_m was reached; call again with start = end_off */
+} ambrycrc_recover_result;
+
+/* The message chain of a region in device memory: ambrycrc_chain_messages_host without the host. From
+ * `start`, a header is accepted when its version is 1..3 and it fits the region, its CRC matches, its
+ * message size is > 0, its first record offset is >= the header size and the message lies inside the
+ * region; the next message starts at first record offset + message size past it.
+ * d_msg_off[0 .. chained) = the starts in log order, d_msg_off[chained .. max_m) = UINT64_MAX.
+ * d_result->end_off is where the walk stopped: region_len (end_status 0), the next start when `more` is set,
+ * or the first position whose header is not accepted, with end_status = AMBRYCRC_MSG_BAD_VERSION (version
+ * not 1..3), _HEADER_CRC, or _BAD_LAYOUT (a size or offset failure, a header or message that overruns the
+ * region, fewer than 2 bytes left: the reference's IndexOutOfBounds, BlobStoreRecovery.java:51,:64).
+ * Every accepted header in [start, region_len) is a node of a forward-pointing graph and the chain is the
+ * path from `start`, found by pointer doubling over the first max_m nodes by position. So `more` can be set
+ * with chained < max_m, when valid headers inside blob content precede the chain's end; without such
+ * headers the result equals ambrycrc_recover_messages_cpu's chain exactly, and with them the concatenation
+ * of the calls a caller makes while `more` is set does.
+ * start == region_len is a clean empty result; start > region_len, max_m == 0 or >= 2^31: AMBRYCRC_EINVAL.
+ * Only enqueues on `stream` (no host synchronisation; capturable with a caller workspace of
+ * ambrycrc_chain_workspace_bytes(region_len, max_m)); d_ws NULL uses the stream's default workspace. */
+size_t ambrycrc_chain_workspace_bytes(uint64_t region_len, size_t max_m);
+int ambrycrc_chain_messages_dev(const uint8_t* d_region, uint64_t region_len, uint64_t start, size_t max_m,
+                                uint64_t* d_msg_off, ambrycrc_recover_result* d_result,
+                                void* d_ws, size_t ws_bytes, hipStream_t stream);
+
+/* BlobStoreRecovery.recover (BlobStoreRecovery.java:43-139) over [start, region_len): the chain above,
+ * ambrycrc_verify_messages_dev's checks on every chained message, then the MessageInfo fields.
+ * d_status[i] = the verify bits | AMBRYCRC_MSG_BAD_INFO for i < chained (AMBRYCRC_MSG_BAD_LAYOUT for the
+ * unused slots, whose offset is UINT64_MAX: the verify runs over all max_m slots, since the chain length is
+ * known only on the device, and an offset past the region is inert there in every verify form);
+ * d_info[i] is filled where the status is 0 and zero elsewhere. d_result->recovered is the length of the
+ * clean prefix; if a chained message fails, end_off is its start, end_status its status and more 0;
+ * otherwise end_off, end_status and more are the chain's. Assumptions as the verify's: records sit where the
+ * header says and the key is opaque bytes. Only enqueues; workspace as above. */
+size_t ambrycrc_recover_workspace_bytes(uint64_t region_len, size_t max_m);
+int ambrycrc_recover_messages_dev(const uint8_t* d_region, uint64_t region_len, uint64_t start, size_t max_m,
+                                  uint64_t* d_msg_off, ambrycrc_message_info* d_info, uint32_t* d_status,
+                                  ambrycrc_recover_result* d_result, void* d_ws, size_t ws_bytes, hipStream_t stream);
+/* The same for a region in host memory: the sequential loop over ambrycrc_verify_message_cpu. It stops
+ * hopping after max_m messages (more = 1 unless it stands at region_len). msg_off, info, status: host
+ * arrays of max_m (info, status nullable). */
+int ambrycrc_recover_messages_cpu(const uint8_t* region, uint64_t region_len, uint64_t start, size_t max_m,
+                                  uint64_t* msg_off, ambrycrc_message_info* info, uint32_t* status,
+                                  ambrycrc_recover_result* result);
+
 /* ------------------------------------- CRC-trailered records (store files, headers) */
 
 /* Item i = [off[i], off[i] + len[i]) ends in the big-endian 8-B CRC (a long, high word zero)
