@@ -134,16 +134,6 @@ bool same_or_disjoint(const uint32_t* a, const uint32_t* b, size_t n) {
   return x + 4 * n <= y || y + 4 * n <= x;
 }
 
-// The long-record list in the job arrays' space (unused in region mode), `bytes` long: records from
-// byte 64 (at most 4,096), then the piece slots.
-void set_long_list(LongList& l, uint8_t* w, size_t bytes) {
-  l.rec = reinterpret_cast<LongRec*>(w + 64);
-  l.cap = (uint32_t)std::min<size_t>(4096, (bytes - 64) / 2 / sizeof(LongRec));
-  const size_t sb = (64 + l.cap * sizeof(LongRec) + 255) & ~size_t(255);
-  l.slot = reinterpret_cast<uint32_t*>(w + sb);
-  l.pcap = (uint32_t)std::min<size_t>(1u << 30, (bytes - sb) / sizeof(uint32_t));
-}
-
 }  // namespace
 
 namespace ambrycrc {
@@ -166,13 +156,51 @@ DevCtx* ctx_current() {
   return ctx_for(dev);
 }
 
-// workspace: byte_start[n+1] | block_sum[B] | block_small[B] | small_total[5] (uint64:
-//            total, start of size classes 1..3 in small_idx, spare) |
-//            small_idx[n] (uint32) | crc_stage[n] (uint32: crc_in as read by the plan),
-//            B = ceil(n / kPlanPerBlock)
-size_t ws_need(size_t n) {
-  const size_t blocks = (n + kPlanPerBlock - 1) / kPlanPerBlock;
-  return ((n + 6 + 2 * blocks) * sizeof(uint64_t) + 2 * n * sizeof(uint32_t) + 255) & ~size_t(255);
+PlanArgs plan_scan_args(const uint64_t* off, const uint64_t* len, size_t n, void* scratch, uint32_t* out,
+                        const uint32_t* gate, const uint32_t* crc_in) {
+  Carver k(scratch);
+  PlanArgs p;
+  plan_scratch(k, n, p);
+  p.gate = gate;
+  p.off = off;
+  p.len = len;
+  p.crc_in = crc_in;
+  p.n = (uint32_t)n;
+  if (!crc_in) p.crc_stage = nullptr;
+  p.out = out;
+  p.small_max = 0;
+  return p;
+}
+
+int enqueue_scan_copy(DevCtx* c, const uint64_t* src, const uint64_t* dst_off, const uint64_t* len,
+                      const uint64_t* cost, size_t n, uint8_t* dst, void* scratch, uint32_t* out,
+                      const uint32_t* gate, hipStream_t s) {
+  const PlanArgs p = plan_scan_args(dst_off, cost, n, scratch, out, gate);
+  if (launch_plan(p, s) != hipSuccess) return AMBRYCRC_EHIP;
+  CopyArgs ca;
+  ca.src = src;
+  ca.dst_off = dst_off;
+  ca.len = len;
+  ca.start = p.byte_start;
+  ca.n = (uint32_t)n;
+  ca.dst = dst;
+  ca.gate = gate;
+  return hip_err(launch_gather_copy(ca, c->num_cu * 8, s));
+}
+
+void region_args(const DevCtx* c, const uint8_t* d_region, uint64_t region_len, size_t m, void* sums, FusedArgs* f) {
+  RegionArgs& r = f->g;
+  const uintptr_t rp = reinterpret_cast<uintptr_t>(d_region);
+  r.base = d_region - (rp & 63u);
+  r.reg0 = rp & 63u;
+  r.reg_end = r.reg0 + region_len;
+  r.lo16 = r.reg0 & ~uint64_t(15);
+  r.hi16 = (r.reg_end - 1) & ~uint64_t(15);
+  r.nsb = region_nsb(d_region, region_len);
+  r.img = c->d_img;
+  Carver k(sums);
+  region_sums(k, d_region, region_len, m, *f);
+  f->ngroups = (r.nsb + 3) / 4;
 }
 
 // Frees retired default workspaces whose last user has completed. Caller holds c->ws_mu.
@@ -287,20 +315,7 @@ int enqueue_batch(DevCtx* c, const uint8_t* base, const uint64_t* off, const uin
                   uint32_t* out, size_t n, void* ws, hipStream_t s, uint32_t* exp_fill, uint8_t* copy_dst,
                   const uint64_t* copy_off, const uint32_t* gate) {
   if (n == 0) return AMBRYCRC_OK;
-  PlanArgs p;
-  p.gate = gate;
-  p.off = off;
-  p.len = len;
-  p.crc_in = crc_in;
-  p.n = (uint32_t)n;
-  p.byte_start = static_cast<uint64_t*>(ws);
-  const size_t blocks = (n + kPlanPerBlock - 1) / kPlanPerBlock;
-  p.block_sum = p.byte_start + n + 1;
-  p.block_small = p.block_sum + blocks;
-  p.small_total = p.block_small + blocks;
-  p.small_idx = reinterpret_cast<uint32_t*>(p.small_total + 5);
-  p.crc_stage = crc_in ? p.small_idx + n : nullptr;
-  p.out = out;
+  PlanArgs p = plan_scan_args(off, len, n, ws, out, gate, crc_in);
   p.small_max = copy_dst ? (n >= kGroupMinChunks ? kGroupSmallMax : 0) : batch_small_max(c, n);
   hipError_t e = launch_plan(p, s);
   if (e != hipSuccess) return AMBRYCRC_EHIP;
@@ -380,13 +395,6 @@ void free_ctx(DevCtx* c) {
   delete c;
 }
 
-// The device message pipeline (parse -> plan + sweep -> reduce) on `stream`; d_ws holds
-// at least ambrycrc_messages_workspace_bytes(m).
-size_t msg_jobs_bytes(size_t m) {
-  const size_t j = (size_t)kMsgSlots * m;
-  return (j * 2 * sizeof(uint64_t) + j * 2 * sizeof(uint32_t) + j + 255) & ~size_t(255);
-}
-
 // A processor wave finishes a 64-message batch in ~20-40 us (a chain of dependent reads under the
 // streamers' load), so the processors a CU needs grow with its messages; the rest of its waves
 // stream, and too few streamers starve them (a cliff: 3 of 12 at 1 KiB blobs, 0.367 -> 0.438 ms).
@@ -428,41 +436,27 @@ int enqueue_messages(DevCtx* c, const uint8_t* d_region, uint64_t region_len, co
   st.a.status = d_status;
   st.a.msg_end = d_msg_end;
   st.a.inline_max = 0;
-  st.batch_ws = static_cast<uint8_t*>(d_ws) + msg_jobs_bytes(m);
-  RegionArgs r;
-  const uintptr_t rp = reinterpret_cast<uintptr_t>(d_region);
-  r.base = d_region - (rp & 63u);
-  r.reg0 = rp & 63u;
-  r.reg_end = r.reg0 + region_len;
-  r.lo16 = r.reg0 & ~uint64_t(15);
-  r.hi16 = (r.reg_end - 1) & ~uint64_t(15);
-  r.nsb = region_nsb(d_region, region_len);
-  r.rk = static_cast<uint32_t*>(st.batch_ws);
-  r.img = c->d_img;
+  Carver jobs(d_ws);
+  msg_jobs(jobs, m, st.a);
+  FusedArgs f;
+  region_args(c, d_region, region_len, m, jobs.here(), &f);
+  // long records (more than region::kLongRuns runs) listed in the job arrays' space, which region
+  // mode does not use
+  Carver k(d_ws);
+  long_list(k, jobs.bytes(), f.g.lng);
   if (c->region_mode == 2) {  // the two-pass form: runs kernel, then one thread per message
-    // long records (more than region::kLongRuns runs) listed in the job arrays' space, which
-    // region mode does not use: the whole grid takes them after pass 2
-    uint8_t* lw = static_cast<uint8_t*>(d_ws);
-    r.lng.ctr = reinterpret_cast<unsigned long long*>(lw);
-    r.lng.claim = reinterpret_cast<uint32_t*>(lw + 8);
-    set_long_list(r.lng, lw, msg_jobs_bytes(m));
+    const RegionArgs& r = f.g;  // the whole grid takes the long records after pass 2
     if (launch_region_runs(r, c->grid, stream) != hipSuccess ||
         launch_region_msg(st.a, r, c->num_cu, stream) != hipSuccess)
       return AMBRYCRC_EHIP;
     return hip_err(launch_region_long(st.a, r, c->num_cu, stream));
   }
-  FusedArgs f;
   f.a = st.a;
-  f.g = r;
-  f.ngroups = (r.nsb + 3) / 4;
-  f.ctl = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(st.batch_ws) + region_rk_bytes(d_region, region_len));
-  f.defer = f.ctl + 64;
   f.nproc = fused_proc_waves(c, m, false);
-  // long records: listed by the processors (records in the job arrays' space, as the two-pass
-  // form's; the counters in ctl, zeroed with it), taken by region_long_kernel after the tail
+  // long records: listed by the processors (the counters in ctl instead, zeroed with it), taken by
+  // region_long_kernel after the tail
   f.g.lng.ctr = reinterpret_cast<unsigned long long*>(f.ctl + 4);
   f.g.lng.claim = f.ctl + 6;
-  set_long_list(f.g.lng, static_cast<uint8_t*>(d_ws), msg_jobs_bytes(m));
   if (hipMemsetAsync(f.ctl, 0, 32, stream) != hipSuccess) return AMBRYCRC_EHIP;
   return hip_err(launch_region_fused(f, c->num_cu, stream));
 }
@@ -471,7 +465,7 @@ int enqueue_messages_parse(DevCtx* c, const uint8_t* d_region, uint64_t region_l
                            size_t m, uint32_t* d_status, uint64_t* d_msg_end, void* d_ws, hipStream_t stream,
                            MsgStage* st, const TransformArgs* desc, const uint32_t* gate) {
   const size_t j = (size_t)kMsgSlots * m;
-  uint8_t* w = static_cast<uint8_t*>(d_ws);
+  Carver k(d_ws);
   MsgArgs& a = st->a;
   a.gate = gate;
   a.region = d_region;
@@ -479,19 +473,14 @@ int enqueue_messages_parse(DevCtx* c, const uint8_t* d_region, uint64_t region_l
   a.msg_off = d_msg_off;
   a.m = m;
   a.img = c->d_img;
-  a.job_off = reinterpret_cast<uint64_t*>(w);
-  a.job_len = a.job_off + j;
-  a.expected = reinterpret_cast<uint32_t*>(a.job_len + j);
-  uint32_t* crc = a.expected + j;
-  a.crc = crc;
+  st->crc = msg_jobs(k, m, a);
   a.status = d_status;
   a.msg_end = d_msg_end;
   // The class-sized group phase (variant 29) reads the stored CRCs of the records it
   // takes whole; the parse kernel reads the rest.
   const bool inline_exp = variant_groups(c->variant);
   a.inline_max = inline_exp ? batch_small_max(c, j) : 0;
-  st->batch_ws = w + msg_jobs_bytes(m);
-  st->crc = crc;
+  st->batch_ws = k.here();
   st->j = j;
   return hip_err(desc ? launch_msg_parse_desc(a, *desc, stream) : launch_msg_parse(a, stream));
 }
@@ -730,11 +719,13 @@ int ambrycrc_verify_dev(const uint8_t* d_base, const uint64_t* d_off, const uint
   DevCtx* c = ctx_current();
   if (!c) return AMBRYCRC_ENOINIT;
   // Without a caller d_out, the CRCs live in the workspace after the batch's own part.
-  const size_t extra = d_out ? 0 : ((n * sizeof(uint32_t) + 255) & ~size_t(255));
+  Carver need(nullptr);
+  verify_scratch(need, n, !d_out);
   WsLease lease;
-  int rc = lease.acquire(c, stream, &d_ws, ws_bytes, ws_need(n) + extra);
+  int rc = lease.acquire(c, stream, &d_ws, ws_bytes, need.bytes());
   if (rc) return rc;
-  if (!d_out) d_out = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_ws) + ws_need(n));
+  Carver k(d_ws);
+  if (!d_out) d_out = verify_scratch(k, n, true);
   rc = enqueue_batch(c, d_base, d_off, d_len, d_crc_in, d_out, n, d_ws, stream);
   if (rc) return rc;
   return hip_err(launch_verify(d_out, d_expected, d_mismatch, d_mismatch_count, (uint32_t)n, stream));
@@ -929,10 +920,7 @@ int ambrycrc_verify_messages_dev(const uint8_t* d_region, uint64_t region_len, c
                           ws_bytes ? ws_bytes : need, stream);
 }
 
-size_t ambrycrc_trailed_workspace_bytes(size_t n) {
-  const size_t own = (n * (sizeof(uint64_t) + 2 * sizeof(uint32_t) + 1) + 255) & ~size_t(255);
-  return own + ws_need(n);
-}
+size_t ambrycrc_trailed_workspace_bytes(size_t n) { return trailed_own_bytes(n) + ws_need(n); }
 
 int ambrycrc_verify_trailed_dev(const uint8_t* d_base, const uint64_t* d_off, const uint64_t* d_len,
                                 uint8_t* d_mismatch, uint32_t* d_mismatch_count, size_t n, void* d_ws,
@@ -944,24 +932,19 @@ int ambrycrc_verify_trailed_dev(const uint8_t* d_base, const uint64_t* d_off, co
   WsLease lease;
   int rc = lease.acquire(c, stream, &d_ws, ws_bytes, ambrycrc_trailed_workspace_bytes(n));
   if (rc) return rc;
-  uint8_t* w = static_cast<uint8_t*>(d_ws);
+  Carver k(d_ws);
   TrailerArgs a;
   a.base = d_base;
   a.off = d_off;
   a.len = d_len;
   a.n = n;
-  a.job_len = reinterpret_cast<uint64_t*>(w);
-  a.expected = reinterpret_cast<uint32_t*>(a.job_len + n);
-  uint32_t* crc = a.expected + n;
-  a.crc = crc;
-  a.force = reinterpret_cast<uint8_t*>(crc + n);
+  uint32_t* crc = trailed_own(k, n, a);
   a.mismatch = d_mismatch;
   a.count = d_mismatch_count;
   const bool inline_exp = variant_groups(c->variant);
   a.inline_max = inline_exp ? batch_small_max(c, n) : 0;
-  void* batch_ws = w + ((n * (sizeof(uint64_t) + 2 * sizeof(uint32_t) + 1) + 255) & ~size_t(255));
   if (launch_trailer_parse(a, stream) != hipSuccess) return AMBRYCRC_EHIP;
-  rc = enqueue_batch(c, d_base, d_off, a.job_len, nullptr, crc, n, batch_ws, stream,
+  rc = enqueue_batch(c, d_base, d_off, a.job_len, nullptr, crc, n, k.here(), stream,
                          a.inline_max ? a.expected : nullptr);
   if (rc) return rc;
   return hip_err(launch_trailer_verify(a, stream));

@@ -12,6 +12,7 @@
 
 #include "../../include/ambrycrc.h"
 #include "crc32_kernels.h"
+#include "ws_layout.h"
 
 namespace ambrycrc {
 namespace detail {
@@ -230,8 +231,6 @@ void host_note_msg(DevCtx* c, int op, bool cpu, uint64_t bytes, double seconds);
 double host_msg_cpu_gibps(const DevCtx* c, int op);
 DevCtx* ctx_for(int device);
 DevCtx* ctx_current();
-// Bytes of batch workspace for n chunks (ambrycrc_workspace_bytes).
-size_t ws_need(size_t n);
 // Default workspaces kept per device: a caller cycling through many short-lived streams (one per
 // request) holds at most this many buffers; the least recently used one is retired behind its
 // last call's event and freed once that work has completed.
@@ -239,6 +238,16 @@ constexpr size_t kMaxStreamWs = 16;
 int stream_ws(DevCtx* c, hipStream_t s, size_t need, void** out, size_t* entry, bool* capturing);
 // Largest chunk the group phase takes whole for a batch of n chunks on c's variant (0: none).
 uint64_t batch_small_max(const DevCtx* c, size_t n);
+// The plan kernel's arguments for a plain exclusive scan of len[0..n) into byte_start, no small-chunk
+// classes (scratch: >= ws_need(n) bytes, laid out by plan_scratch; out: the plan's per-chunk
+// initialisation lands there; gate: PlanArgs::gate; crc_in: the batch engine's, staged in the scratch).
+PlanArgs plan_scan_args(const uint64_t* off, const uint64_t* len, size_t n, void* scratch, uint32_t* out,
+                        const uint32_t* gate = nullptr, const uint32_t* crc_in = nullptr);
+// That scan over the jobs' costs, then the gather copy of the n jobs (src, dst_off, len: CopyArgs) into
+// dst, balanced by cost over num_cu * 8 workgroups.
+int enqueue_scan_copy(DevCtx* c, const uint64_t* src, const uint64_t* dst_off, const uint64_t* len,
+                      const uint64_t* cost, size_t n, uint8_t* dst, void* scratch, uint32_t* out,
+                      const uint32_t* gate, hipStream_t s);
 // Plan + CRC kernels for n chunks on stream s (ws: >= ws_need(n) bytes). exp_fill, copy_dst,
 // copy_off: see SweepArgs (copy_dst set: the copy-through kernel, whatever c's variant).
 int enqueue_batch(DevCtx* c, const uint8_t* base, const uint64_t* off, const uint64_t* len, const uint32_t* crc_in,
@@ -253,8 +262,10 @@ int enqueue_messages(DevCtx* c, const uint8_t* d_region, uint64_t region_len, co
                      uint32_t* d_status, uint64_t* d_msg_end, void* d_ws, size_t ws_bytes, hipStream_t stream);
 // Processor waves per workgroup of the one-pass region kernels for m messages (FusedArgs::nproc).
 uint32_t fused_proc_waves(const DevCtx* c, size_t m, bool copy);
-// Bytes of the job arrays at the start of a message-verify workspace (the rest: batch / run sums).
-size_t msg_jobs_bytes(size_t m);
+// The 64-B run geometry of a region (f->g: base, reg0, reg_end, lo16, hi16, nsb, img) with its sums
+// area at `sums` (region_sums: rk, and the one-pass form's ctl and defer for m messages), and the
+// one-pass form's group count.
+void region_args(const DevCtx* c, const uint8_t* d_region, uint64_t region_len, size_t m, void* sums, FusedArgs* f);
 // The same in two halves: the parse kernel (jobs and their stored CRCs in st->a), then the CRC
 // batch and the reduce -- with copy_dst / copy_off, the batch is the copy-through kernel
 // (SweepArgs::copy_dst), which the transform uses to copy the records while verifying them.

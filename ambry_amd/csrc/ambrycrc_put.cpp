@@ -15,34 +15,6 @@
 using namespace ambrycrc;
 using namespace ambrycrc::detail;
 
-namespace {
-
-// Workspace of a device batch of m messages: copy jobs (src, dst, len, cost) and CRC jobs (off, len,
-// crc, crc_in) of 5 per message, then one batch workspace shared by the copy plan and the CRC batch
-// (both run on the same stream, one after the other).
-size_t put_jobs_bytes(size_t m) {
-  const size_t j = (size_t)kPutSlots * m;
-  return (j * (4 * sizeof(uint64_t) + 2 * sizeof(uint64_t) + 2 * sizeof(uint32_t)) + 255) & ~size_t(255);
-}
-
-// The job path's workspace (copy and CRC jobs, the batch workspace, the streamed form's `big` word);
-// ambrycrc_serialize_puts_workspace_bytes adds the streamed form's run slots after it (the transform,
-// which never streams, uses this much).
-size_t put_core_bytes(size_t m) { return put_jobs_bytes(m) + ws_need((size_t)kPutSlots * m) + 256; }
-
-// A transform's own workspace: descriptors, the scan's per-message output, in_crc (4 per message),
-// the speculative pass's xstatus, its fail flag, the verify jobs' copy destinations (5 per message)
-// and the properties re-encodings (one PropsFix per message).
-size_t transform_head_bytes(size_t m) {
-  return (m * (sizeof(ambrycrc_put_desc) + 6 * sizeof(uint32_t)) + 8 + 15) & ~size_t(15);
-}
-size_t transform_own_bytes(size_t m) {
-  return (transform_head_bytes(m) + (size_t)kPutSlots * m * sizeof(uint64_t) + m * sizeof(PropsFix) + 255) &
-         ~size_t(255);
-}
-
-}  // namespace
-
 namespace ambrycrc {
 namespace detail {
 
@@ -51,22 +23,14 @@ int enqueue_serialize(DevCtx* c, const ::ambrycrc_put_desc* d_desc, size_t m, co
                       const uint32_t* d_in_crc, bool layout_only, const uint32_t* gate, const PropsFix* pfix,
                       bool stream_ok) {
   const size_t j = (size_t)kPutSlots * m;
-  uint8_t* w = static_cast<uint8_t*>(d_ws);
+  Carver k(d_ws);
   PutArgs a;
   a.desc = d_desc;
   a.m = m;
   a.out = d_out;
   a.fields = d_fields;
   a.blobs = d_blobs;
-  a.cp_src = reinterpret_cast<uint64_t*>(w);
-  a.cp_dst = a.cp_src + j;
-  a.cp_len = a.cp_dst + j;
-  a.cp_cost = a.cp_len + j;
-  a.crc_off = a.cp_cost + j;
-  a.crc_len = a.crc_off + j;
-  uint32_t* crc = reinterpret_cast<uint32_t*>(a.crc_len + j);
-  a.crc = crc;
-  a.crc_in = crc + j;
+  const PutCore w = put_core(k, m, a);
   a.msg_len = d_msg_len;
   a.in_crc = d_in_crc;
   a.img = c->d_img;
@@ -81,7 +45,6 @@ int enqueue_serialize(DevCtx* c, const ::ambrycrc_put_desc* d_desc, size_t m, co
     a.src_base = (uint64_t)lo & ~uint64_t(255);  // offsets keep their addresses' alignment
   }
   a.pfix = pfix;
-  void* batch_ws = w + put_jobs_bytes(m);
   // Copy mode with both sources (round 6): messages of at most stream_put_max bytes are
   // streamed -- put_stream_kernel writes each whole and keeps its output runs' CRCs, put_stream_seal_kernel
   // writes its trailers -- and the layout kernel gives them no jobs; a longer one sets `big`, which gates
@@ -90,7 +53,7 @@ int enqueue_serialize(DevCtx* c, const ::ambrycrc_put_desc* d_desc, size_t m, co
   StreamPutArgs sa;
   if (streamed) {
     a.stream_max = (uint32_t)c->stream_put_max;
-    a.big = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(batch_ws) + ws_need(j));
+    a.big = w.big;
     if (hipMemsetAsync(a.big, 0, sizeof(uint32_t), stream) != hipSuccess) return AMBRYCRC_EHIP;
     sa.desc = d_desc;
     sa.m = m;
@@ -98,7 +61,7 @@ int enqueue_serialize(DevCtx* c, const ::ambrycrc_put_desc* d_desc, size_t m, co
     sa.oreg0 = reinterpret_cast<uintptr_t>(d_out) & 63u;
     sa.fields = d_fields;
     sa.blobs = d_blobs;
-    sa.rk = reinterpret_cast<uint32_t*>(w + put_core_bytes(m));
+    sa.rk = static_cast<uint32_t*>(k.here());  // the run slots (stream_put_rk_bytes), after the job path's part
     sa.img = c->d_img;
   }
   if (launch_put_layout(a, stream) != hipSuccess) return AMBRYCRC_EHIP;
@@ -115,41 +78,19 @@ int enqueue_serialize(DevCtx* c, const ::ambrycrc_put_desc* d_desc, size_t m, co
     // one pass over the fields: the copy-through sweep reads each from its source, writes it into
     // the message and CRCs it (job k*m+i = slot k of message i, as the CRC jobs)
     const int rc = enqueue_batch(c, reinterpret_cast<const uint8_t*>((uintptr_t)a.src_base), a.cp_src, a.cp_len,
-                                 a.crc_in, crc, j, batch_ws, stream, nullptr, d_out, a.cp_dst, a.gate);
+                                 a.crc_in, w.crc, j, w.batch_ws, stream, nullptr, d_out, a.cp_dst, a.gate);
     if (rc) return rc;
     return hip_err(launch_put_seal(a, stream));
   }
   if (d_fields || d_blobs) {
     // cost offsets of the copy jobs: the plan kernel's exclusive scan (no small-chunk classes);
     // its per-chunk output initialisation lands in `crc`, overwritten by the CRC batch below
-    PlanArgs p;
-    p.gate = gate;  // the transform's fallback pass: only when a placed message failed
-    p.off = a.cp_dst;
-    p.len = a.cp_cost;
-    p.crc_in = nullptr;
-    p.n = (uint32_t)j;
-    p.byte_start = static_cast<uint64_t*>(batch_ws);
-    const size_t blocks = (j + kPlanPerBlock - 1) / kPlanPerBlock;
-    p.block_sum = p.byte_start + j + 1;
-    p.block_small = p.block_sum + blocks;
-    p.small_total = p.block_small + blocks;
-    p.small_idx = reinterpret_cast<uint32_t*>(p.small_total + 5);
-    p.crc_stage = nullptr;
-    p.out = crc;
-    p.small_max = 0;
-    if (launch_plan(p, stream) != hipSuccess) return AMBRYCRC_EHIP;
-    CopyArgs ca;
-    ca.src = a.cp_src;
-    ca.dst_off = a.cp_dst;
-    ca.len = a.cp_len;
-    ca.start = p.byte_start;
-    ca.n = (uint32_t)j;
-    ca.dst = d_out;
-    ca.gate = gate;
-    if (launch_gather_copy(ca, c->num_cu * 8, stream) != hipSuccess) return AMBRYCRC_EHIP;
+    // (gate: the transform's fallback pass, only when a placed message failed)
+    const int rc = enqueue_scan_copy(c, a.cp_src, a.cp_dst, a.cp_len, a.cp_cost, j, d_out, w.batch_ws, w.crc, gate, stream);
+    if (rc) return rc;
   }
   if (d_in_crc) return AMBRYCRC_OK;  // the layout kernel wrote every trailer
-  const int rc = enqueue_batch(c, d_out, a.crc_off, a.crc_len, nullptr, crc, j, batch_ws, stream);
+  const int rc = enqueue_batch(c, d_out, a.crc_off, a.crc_len, nullptr, w.crc, j, w.batch_ws, stream);
   if (rc) return rc;
   return hip_err(launch_put_seal(a, stream));
 }
@@ -216,14 +157,6 @@ size_t ambrycrc_transform_workspace_bytes(size_t m) {
 }
 
 namespace {
-// The one-pass fast path keeps its run sums, control words and deferred list where the general
-// path's verify / serializer workspace goes (it runs first, on the same stream).
-size_t transform_fast_bytes(const uint8_t* d_region, uint64_t region_len, size_t m) {
-  return region_ws_bytes(d_region, region_len, m);
-}
-}  // namespace
-
-namespace {
 // The side-stream verdict's entry for caller stream s (c->xs_mu held): its own, else a new one, else the
 // least recently used re-keyed to s (DevCtx::XformSide). Null when one cannot be made.
 DevCtx::XformSide* xform_side_for(DevCtx* c, hipStream_t s) {
@@ -284,7 +217,9 @@ int ambrycrc_transform_messages_dev(const uint8_t* d_region, uint64_t region_len
   // Fast path (FusedArgs::out): header V3 out, region mode on, a region to sweep, and workspace room
   // for the run sums (the library's own workspace is sized for them; a caller's as given).
   const size_t base_need = ambrycrc_transform_workspace_bytes(m);
-  const size_t fast_need = transform_own_bytes(m) + ws_need(m) + transform_fast_bytes(d_region, region_len, m);
+  // (the fast path keeps its run sums, control words and deferred list where the general path's verify /
+  // serializer workspace goes: it runs first, on the same stream)
+  const size_t fast_need = transform_own_bytes(m) + ws_need(m) + region_ws_bytes(d_region, region_len, m);
   const bool want_fast = header_version == 3 && c->region_mode != 0 && region_len > 0 &&
                          region_len <= c->xform_fast_max * (uint64_t)m;
   const size_t need = want_fast && !d_ws ? std::max(base_need, fast_need) : base_need;
@@ -292,10 +227,9 @@ int ambrycrc_transform_messages_dev(const uint8_t* d_region, uint64_t region_len
   int rc = lease.acquire(c, stream, &d_ws, ws_bytes, need);
   if (rc) return rc;
   const bool fast = want_fast && (ws_bytes ? ws_bytes : need) >= fast_need;
-  // workspace: desc[m] | scan scratch (uint32 per message) | in_crc[4m] | xstatus[m] | fail |
-  //            copy_off[5m] | pfix[m] | plan workspace for the m lengths | the verify pipeline's, then the
-  //            serializer's (one after the other on the stream)
-  uint8_t* w = static_cast<uint8_t*>(d_ws);
+  // workspace: the transform's own area (transform_own) | the plan scratch for the m lengths | the verify
+  //            pipeline's, then the serializer's (one after the other on the stream)
+  Carver k(d_ws);
   TransformArgs t;
   memset(&t, 0, sizeof t);
   t.region = d_region;
@@ -304,38 +238,19 @@ int ambrycrc_transform_messages_dev(const uint8_t* d_region, uint64_t region_len
   t.m = m;
   t.life = d_life_version;
   t.header_version = header_version;
-  t.desc = reinterpret_cast<ambrycrc_put_desc*>(w);
+  const TransformOwn own = transform_own(k, m, t);
+  uint32_t* fail = own.fail;
   t.out_len = d_out_len;
   t.out_off = d_out_off;
   t.status = d_status;
   t.out_cap = out_cap;
-  uint32_t* scan_out = reinterpret_cast<uint32_t*>(w + m * sizeof(ambrycrc_put_desc));
-  t.in_crc = scan_out + m;
-  uint32_t* xstatus = t.in_crc + 4 * m;
-  uint32_t* fail = xstatus + m;
-  uint64_t* copy_off = reinterpret_cast<uint64_t*>(w + transform_head_bytes(m));
-  t.pfix = reinterpret_cast<PropsFix*>(copy_off + (size_t)kPutSlots * m);
   t.img = c->d_img;
   t.out = d_out;
   t.fail = fail;
-  uint8_t* plan_ws = w + transform_own_bytes(m);
-  void* shared = plan_ws + ws_need(m);
   // packed output offsets: the plan kernel's exclusive scan of the output lengths
-  PlanArgs p;
-  p.gate = nullptr;
-  p.off = d_msg_off;
-  p.len = d_out_len;
-  p.crc_in = nullptr;
-  p.n = (uint32_t)m;
-  p.byte_start = reinterpret_cast<uint64_t*>(plan_ws);
-  const size_t blocks = (m + kPlanPerBlock - 1) / kPlanPerBlock;
-  p.block_sum = p.byte_start + m + 1;
-  p.block_small = p.block_sum + blocks;
-  p.small_total = p.block_small + blocks;
-  p.small_idx = reinterpret_cast<uint32_t*>(p.small_total + 5);
-  p.crc_stage = nullptr;
-  p.out = scan_out;
-  p.small_max = 0;
+  PlanArgs p = plan_scan_args(d_msg_off, d_out_len, m, k.here(), own.scan_out);
+  k.take<uint8_t>(ws_need(m));  // (that scan's scratch)
+  void* shared = k.here();
 
   // Speculative pass (two HBM passes: the verify reads every record once and writes the ones the
   // output keeps into place). The descriptors and the packed placement come from the parse alone,
@@ -360,29 +275,18 @@ int ambrycrc_transform_messages_dev(const uint8_t* d_region, uint64_t region_len
     f.a.status = d_status;
     f.a.msg_end = nullptr;
     f.a.inline_max = 0;
-    const uintptr_t rp = reinterpret_cast<uintptr_t>(d_region);
-    f.g.base = d_region - (rp & 63u);
-    f.g.reg0 = rp & 63u;
-    f.g.reg_end = f.g.reg0 + region_len;
-    f.g.lo16 = f.g.reg0 & ~uint64_t(15);
-    f.g.hi16 = (f.g.reg_end - 1) & ~uint64_t(15);
-    f.g.nsb = region_nsb(d_region, region_len);
-    f.g.rk = reinterpret_cast<uint32_t*>(shared);
-    f.g.img = c->d_img;
-    f.ngroups = (f.g.nsb + 3) / 4;
-    f.ctl = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(shared) + region_rk_bytes(d_region, region_len));
-    f.defer = f.ctl + 64;
+    region_args(c, d_region, region_len, m, shared, &f);
     f.nproc = fused_proc_waves(c, m, true);
     f.out = d_out;
     f.out_cap = out_cap;
     f.out_off = d_out_off;
     f.out_len = d_out_len;
     f.life = d_life_version;
-    f.xstatus = xstatus;
+    f.xstatus = own.xstatus;
     // xfail beside `fail`, outside the shared workspace: the general path's kernels reuse `shared`
     // (ctl included) and read their device gate, *xfail, at every launch
     f.xfail = fail + 1;
-    f.patch = copy_off;  // (the general path's, unused until then)
+    f.patch = own.copy_off;  // (the general path's, unused until then)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &cap) != hipSuccess) return AMBRYCRC_EHIP;
     const int slot = c->xform_host_verdict && cap == hipStreamCaptureStatusNone ? c->take_host_word() : -1;
@@ -455,8 +359,8 @@ int ambrycrc_transform_messages_dev(const uint8_t* d_region, uint64_t region_len
   t.gate = general;
   t.gate_when = 1;
   MsgStage ms;
-  t.xstatus = xstatus;
-  t.copy_off = copy_off;
+  t.xstatus = own.xstatus;
+  t.copy_off = own.copy_off;
   // the parse kernel describes each message as it parses it (transform_desc_kernel fused)
   rc = enqueue_messages_parse(c, d_region, region_len, d_msg_off, m, d_status, nullptr, shared, stream, &ms, &t,
                               general);
@@ -465,7 +369,7 @@ int ambrycrc_transform_messages_dev(const uint8_t* d_region, uint64_t region_len
   if (launch_plan(p, stream) != hipSuccess) return AMBRYCRC_EHIP;
   if (launch_transform_place(t, p.byte_start, stream) != hipSuccess) return AMBRYCRC_EHIP;
   if (launch_transform_jobs(t, stream) != hipSuccess) return AMBRYCRC_EHIP;
-  rc = enqueue_messages_check(c, ms, stream, d_out, copy_off);
+  rc = enqueue_messages_check(c, ms, stream, d_out, own.copy_off);
   if (rc) return rc;
   if (launch_transform_finish(t, stream) != hipSuccess) return AMBRYCRC_EHIP;
   rc = enqueue_serialize(c, t.desc, m, d_region, d_region, d_out, nullptr, shared, stream, t.in_crc, true, general);

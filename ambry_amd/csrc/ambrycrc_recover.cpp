@@ -15,29 +15,14 @@ using namespace ambrycrc::detail;
 
 namespace {
 
-// Scan blocks of any [start, region_len) of a region at any address: the span plus a leading granule.
-uint64_t max_scan_blocks(uint64_t region_len) { return (region_len + 15) / kScanBlock + 1; }
-
-size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
-
-uint64_t tiles_of(uint64_t blocks) { return (blocks + kSumTile - 1) / kSumTile; }
-
-// Workspace: the head, the 8-B arrays (pos, next, the tile sums), the 4-B ones (jump x 2, ord, the block
-// counts and first indices), then the staged 2-B offsets.
-size_t chain_bytes(uint64_t region_len, size_t max_m) {
-  const uint64_t nb = max_scan_blocks(region_len);
-  return align256(sizeof(ChainHead) + max_m * (2 * sizeof(uint64_t) + 3 * sizeof(uint32_t)) +
-                  tiles_of(nb) * sizeof(uint64_t) + nb * (2 * sizeof(uint32_t) + kStageMax * sizeof(uint16_t)));
-}
-
 bool args_ok(const uint8_t* d_region, uint64_t region_len, uint64_t start, size_t max_m) {
   return (d_region || region_len == 0) && start <= region_len && max_m != 0 && max_m < (1ull << 31);
 }
 
 int enqueue_chain(DevCtx* c, const uint8_t* d_region, uint64_t region_len, uint64_t start, size_t max_m,
                   uint64_t* d_msg_off, ambrycrc_recover_result* d_result, void* d_ws, hipStream_t stream,
-                  ChainArgs* out) {
-  uint8_t* w = static_cast<uint8_t*>(d_ws);
+                  ChainArgs* out, void** rest) {
+  Carver ws(d_ws);
   ChainArgs a;
   a.region = d_region;
   a.region_len = region_len;
@@ -46,18 +31,9 @@ int enqueue_chain(DevCtx* c, const uint8_t* d_region, uint64_t region_len, uint6
   a.img = c->d_img;
   const uint64_t lead = reinterpret_cast<uintptr_t>(d_region + start) & 15u;
   a.nblocks = (lead + (region_len - start) + kScanBlock - 1) / kScanBlock;
-  a.head = reinterpret_cast<ChainHead*>(w);
-  a.pos = reinterpret_cast<uint64_t*>(w + sizeof(ChainHead));
-  a.next = a.pos + max_m;
-  a.ntiles = tiles_of(a.nblocks);
-  const uint64_t nb = max_scan_blocks(region_len);
-  a.part = a.next + max_m;
-  a.jump[0] = reinterpret_cast<uint32_t*>(a.part + tiles_of(nb));
-  a.jump[1] = a.jump[0] + max_m;
-  a.ord = a.jump[1] + max_m;
-  a.cnt = a.ord + max_m;
-  a.blk = a.cnt + nb;
-  a.stage = reinterpret_cast<uint16_t*>(a.blk + nb);
+  a.ntiles = chain_tiles(a.nblocks);
+  chain_ws(ws, region_len, max_m, a);
+  *rest = ws.here();  // recover: the verify's workspace
   a.msg_off = d_msg_off;
   a.result = d_result;
   a.info = nullptr;
@@ -91,7 +67,8 @@ int ambrycrc_chain_messages_dev(const uint8_t* d_region, uint64_t region_len, ui
   const int rc = lease.acquire(c, stream, &d_ws, ws_bytes, chain_bytes(region_len, max_m));
   if (rc) return rc;
   ChainArgs a;
-  return enqueue_chain(c, d_region, region_len, start, max_m, d_msg_off, d_result, d_ws, stream, &a);
+  void* rest;
+  return enqueue_chain(c, d_region, region_len, start, max_m, d_msg_off, d_result, d_ws, stream, &a, &rest);
 }
 
 size_t ambrycrc_recover_workspace_bytes(uint64_t region_len, size_t max_m) {
@@ -110,13 +87,13 @@ int ambrycrc_recover_messages_dev(const uint8_t* d_region, uint64_t region_len, 
   int rc = lease.acquire(c, stream, &d_ws, ws_bytes, ambrycrc_recover_workspace_bytes(region_len, max_m));
   if (rc) return rc;
   ChainArgs a;
-  rc = enqueue_chain(c, d_region, region_len, start, max_m, d_msg_off, d_result, d_ws, stream, &a);
+  void* verify_ws;
+  rc = enqueue_chain(c, d_region, region_len, start, max_m, d_msg_off, d_result, d_ws, stream, &a, &verify_ws);
   if (rc) return rc;
   // the verify over all max_m slots: the unused ones hold UINT64_MAX, an offset past the region, which
   // every verify form answers with AMBRYCRC_MSG_BAD_LAYOUT without reading anything
   if (region_len) {
-    rc = enqueue_messages(c, d_region, region_len, d_msg_off, max_m, d_status, nullptr,
-                          static_cast<uint8_t*>(d_ws) + chain_bytes(region_len, max_m),
+    rc = enqueue_messages(c, d_region, region_len, d_msg_off, max_m, d_status, nullptr, verify_ws,
                           ambrycrc_messages_workspace_bytes(max_m), stream);
     if (rc) return rc;
   }

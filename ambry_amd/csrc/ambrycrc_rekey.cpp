@@ -16,42 +16,6 @@
 using namespace ambrycrc;
 using namespace ambrycrc::detail;
 
-namespace {
-
-// Workspace of m messages: put descriptors (80 B), RekeyFix (16 B), the content CRC jobs (off, len) and
-// the 4m copy jobs (src, dst, len, cost) of 8 B, then the 4-B arrays: the placement scan's per-message
-// output, the content CRCs, the copy scan's per-job output. After it one shared area, used in turn by
-// the verify, the placement scan, the content CRC batch and the copy scan (same stream, one after the other).
-size_t rekey_own_bytes(size_t m) {
-  return (m * (sizeof(ambrycrc_put_desc) + sizeof(RekeyFix) + 2 * sizeof(uint64_t) +
-               (size_t)kRekeySlots * 4 * sizeof(uint64_t) + (2 + (size_t)kRekeySlots) * sizeof(uint32_t)) +
-          255) &
-         ~size_t(255);
-}
-
-// The plan kernel's exclusive scan of len[0..n) into byte_start (no small-chunk classes), as the
-// serializer's copy plan uses it.
-PlanArgs scan_args(const uint64_t* off, const uint64_t* len, size_t n, void* ws, uint32_t* out) {
-  PlanArgs p;
-  p.gate = nullptr;
-  p.off = off;
-  p.len = len;
-  p.crc_in = nullptr;
-  p.n = (uint32_t)n;
-  p.byte_start = static_cast<uint64_t*>(ws);
-  const size_t blocks = (n + kPlanPerBlock - 1) / kPlanPerBlock;
-  p.block_sum = p.byte_start + n + 1;
-  p.block_small = p.block_sum + blocks;
-  p.small_total = p.block_small + blocks;
-  p.small_idx = reinterpret_cast<uint32_t*>(p.small_total + 5);
-  p.crc_stage = nullptr;
-  p.out = out;
-  p.small_max = 0;
-  return p;
-}
-
-}  // namespace
-
 extern "C" {
 
 size_t ambrycrc_rekey_workspace_bytes(size_t m) {
@@ -79,7 +43,7 @@ int ambrycrc_rekey_messages_dev(const uint8_t* d_region, uint64_t region_len, co
   int rc = lease.acquire(c, stream, &d_ws, ws_bytes, ambrycrc_rekey_workspace_bytes(m));
   if (rc) return rc;
   const size_t j = (size_t)kRekeySlots * m;
-  uint8_t* w = static_cast<uint8_t*>(d_ws);
+  Carver k(d_ws);
   RekeyArgs a;
   a.region = d_region;
   a.region_len = region_len;
@@ -90,23 +54,14 @@ int ambrycrc_rekey_messages_dev(const uint8_t* d_region, uint64_t region_len, co
   a.aux_len = aux_len;
   a.life = d_life_version;
   a.header_version = header_version;
-  a.desc = reinterpret_cast<ambrycrc_put_desc*>(w);
-  a.fix = reinterpret_cast<RekeyFix*>(a.desc + m);
-  a.cjob_off = reinterpret_cast<uint64_t*>(a.fix + m);
-  a.cjob_len = a.cjob_off + m;
-  a.cp_src = a.cjob_len + m;
-  a.cp_dst = a.cp_src + j;
-  a.cp_len = a.cp_dst + j;
-  a.cp_cost = a.cp_len + j;
-  uint32_t* scan_out = reinterpret_cast<uint32_t*>(a.cp_cost + j);
-  uint32_t* ccrc = scan_out + m;
-  uint32_t* cp_scan_out = ccrc + m;
-  a.ccrc = ccrc;
+  const RekeyOwn w = rekey_own(k, m, a);
   a.out_len = d_out_len;
   a.status = d_status;
   a.out = d_out;
   a.img = c->d_img;
-  void* shared = w + rekey_own_bytes(m);
+  // after the own area one shared area, used in turn by the verify, the placement scan, the content CRC
+  // batch and the copy scan (same stream, one after the other)
+  void* shared = k.here();
 
   // 1. the message verify (job mode), into d_status
   MsgStage ms;
@@ -118,7 +73,7 @@ int ambrycrc_rekey_messages_dev(const uint8_t* d_region, uint64_t region_len, co
   if (launch_rekey_plan(a, stream) != hipSuccess) return AMBRYCRC_EHIP;
   // 3. packed placement: exclusive scan of the lengths, then the transform's place step (NO_ROOM
   //    for a message past out_cap, which still advances the running offset)
-  const PlanArgs p = scan_args(d_msg_off, d_out_len, m, shared, scan_out);
+  const PlanArgs p = plan_scan_args(d_msg_off, d_out_len, m, shared, w.scan_out);
   if (launch_plan(p, stream) != hipSuccess) return AMBRYCRC_EHIP;
   TransformArgs t;
   memset(&t, 0, sizeof t);
@@ -131,21 +86,11 @@ int ambrycrc_rekey_messages_dev(const uint8_t* d_region, uint64_t region_len, co
   if (launch_transform_place(t, p.byte_start, stream) != hipSuccess) return AMBRYCRC_EHIP;
   // 4. the replacement contents' CRCs (one job a message over aux; most are empty and read nothing),
   //    then header, record heads, properties and every trailer
-  rc = enqueue_batch(c, a.aux, a.cjob_off, a.cjob_len, nullptr, ccrc, m, shared, stream);
+  rc = enqueue_batch(c, a.aux, a.cjob_off, a.cjob_len, nullptr, w.ccrc, m, shared, stream);
   if (rc) return rc;
   if (launch_rekey_write(a, stream) != hipSuccess) return AMBRYCRC_EHIP;
   // 5. the bodies, balanced by cost over the whole grid
-  const PlanArgs q = scan_args(a.cp_dst, a.cp_cost, j, shared, cp_scan_out);
-  if (launch_plan(q, stream) != hipSuccess) return AMBRYCRC_EHIP;
-  CopyArgs ca;
-  ca.src = a.cp_src;
-  ca.dst_off = a.cp_dst;
-  ca.len = a.cp_len;
-  ca.start = q.byte_start;
-  ca.n = (uint32_t)j;
-  ca.dst = d_out;
-  ca.gate = nullptr;
-  return hip_err(launch_gather_copy(ca, c->num_cu * 8, stream));
+  return enqueue_scan_copy(c, a.cp_src, a.cp_dst, a.cp_len, a.cp_cost, j, d_out, shared, w.cp_scan_out, nullptr, stream);
 }
 
 }  // extern "C"

@@ -43,6 +43,18 @@ def assert_untouched(whole, view, data, shift: int = 0):
     assert torch.equal(view.cpu(), torch.from_numpy(np.array(a, copy=True))), "the call changed its input"
 
 
+def guarded_workspace(nbytes):
+    """(the whole tensor, the view) of a caller workspace of exactly nbytes between two 64-B guards, the workspace
+    itself filled with 0xA5 as the guards are: a call must neither rely on what it holds nor write past it."""
+    return guarded(np.full(nbytes, 0xA5, dtype=np.uint8))
+
+
+def assert_guards(whole, view):
+    n = view.numel()
+    assert bool((whole[:GUARD] == 0xA5).all()), "bytes written below the workspace"
+    assert bool((whole[GUARD + n:] == 0xA5).all()), "bytes written past the workspace"
+
+
 def assert_messages(lat, shift, order, status, msg_end, what):
     """status / msg_end (device tensors, in `order`) against the oracle's; names the first failing message and
     the cells() of its probed span as the kernels see it (from the 64-aligned base below the region)."""
@@ -239,4 +251,33 @@ def test_trailed_verify_over_the_chunk_lattice(gpu):
         raise AssertionError("%d flags differ; first item %d: %s, expected %s; %s" % (
             int((got != tr.bad).sum()), i, got[i], tr.bad[i], vars(G.cells(int(tr.off[i]), int(tr.length[i]) - 8))))
     assert int(count.item()) == int(tr.bad.sum())
+    assert_untouched(whole, mem, tr.mem)
+
+
+@pytest.mark.parametrize("n", [1, 2048, 2049])
+def test_trailed_verify_exact_workspace(gpu, n):
+    """ambrycrc_verify_trailed_dev with a caller workspace of exactly ambrycrc_trailed_workspace_bytes(n) between
+    guards: one item, and the counts on either side of one plan block (2,048 jobs). The first n lattice items,
+    flags and count as the oracle's; both guards intact."""
+    import ctypes
+
+    import torch
+
+    from ambry_amd._lib import check, lib
+
+    tr = G.trailed_lattice()
+    bad = tr.bad[:n]
+    assert n == 1 or (bad.any() and not bad.all())  # corrupt and clean items both
+    whole, mem = guarded(tr.mem)
+    off, ln = torch.from_numpy(tr.off[:n].copy()).cuda(), torch.from_numpy(tr.length[:n].copy()).cuda()
+    mism = torch.empty(n, dtype=torch.uint8, device="cuda")
+    count = torch.zeros(1, dtype=torch.int32, device="cuda")
+    wwhole, ws = guarded_workspace(lib().ambrycrc_trailed_workspace_bytes(n))
+    check(lib().ambrycrc_verify_trailed_dev(mem.data_ptr(), off.data_ptr(), ln.data_ptr(), mism.data_ptr(),
+                                            count.data_ptr(), n, ws.data_ptr(), ws.numel(), ctypes.c_void_p(0)),
+          "ambrycrc_verify_trailed_dev")
+    torch.cuda.synchronize()
+    assert_guards(wwhole, ws)
+    assert np.array_equal(mism.cpu().numpy().astype(bool), bad)
+    assert int(count.item()) == int(bad.sum())
     assert_untouched(whole, mem, tr.mem)

@@ -40,13 +40,13 @@ def to_dev(info):
     return torch.from_numpy(np.ascontiguousarray(info).view(np.uint8).reshape(len(info), 32)).cuda()
 
 
-def run_gpu(gpu, region: bytes, offs, shift=0, recovery=None, plan_only=False):
+def run_gpu(gpu, region: bytes, offs, shift=0, recovery=None, plan_only=False, workspace=None):
     import torch
 
     whole, r = place(region, shift)
     o = torch.tensor(np.asarray(offs, dtype=np.int64), device="cuda")
     status, info = gpu.hard_delete_messages(r, o, recovery=None if recovery is None else to_dev(recovery),
-                                            plan_only=plan_only)
+                                            plan_only=plan_only, workspace=workspace)
     torch.cuda.synchronize()
     return (status.cpu().numpy().view(np.uint32).tolist(), info.cpu().numpy().reshape(-1).view(HD.INFO),
             read_back(whole, shift, len(region)))
@@ -72,6 +72,33 @@ def test_region_matches_oracle_and_cpu(gpu, seed, shift):
     assert out == eout
     if shift == 0:
         assert (st, out) == HD.run_cpu(gpu, region, offs)[::2]
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case(m):
+    """m small messages, 10 % corrupted (build_region's first message, the one with a blob of 60 KB and more,
+    left out), and the oracle's answers."""
+    region, offs, _ = build_region(n=m + 1, seed=700 + m, corrupt_frac=0.1 if m > 1 else 0.0, big_every=10**9)
+    region, offs = region[offs[1]:], [o - offs[1] for o in offs[1:]]
+    return region, offs, HD.hard_delete(region, offs)
+
+
+@pytest.mark.parametrize("m", [1, 1024, 1025])
+def test_exact_workspace_between_guards(gpu, m):
+    """A caller workspace of exactly ambrycrc_hard_delete_workspace_bytes(m) between two guards, 0xA5
+    throughout: one message, and the counts on either side of one plan block (2 jobs a message: 2,048 / 2,050
+    jobs). Status, info and every region byte as the oracle's; the workspace's guards intact."""
+    from test_gpu_geometry import assert_guards, guarded_workspace
+
+    region, offs, (est, einfo, eout) = exact_case(m)
+    deleted, refused, not_put, _ = HD.counts(region, offs, est)
+    assert (deleted, refused, not_put) == (1, 0, 0) if m == 1 else deleted >= 700 and refused >= 50 and not_put >= 50
+    whole, ws = guarded_workspace(gpu.hard_delete_workspace_bytes(m))
+    st, info, out = run_gpu(gpu, region, offs, shift=13, workspace=ws)
+    assert_guards(whole, ws)
+    assert st == est
+    assert np.array_equal(info, einfo)
+    assert out == eout
 
 
 def test_alignment_grid(gpu):

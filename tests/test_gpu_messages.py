@@ -4,6 +4,7 @@ Bit-exact per-message status and message-end offsets on log regions mixing PUT
 messages (header V1/V2/V3, with and without encryption-key records, blobs from
 0 B to ~300 KB) and update messages, with random single-bit corruptions, an
 unknown header version and a message truncated by the region end."""
+import functools
 import struct
 
 import numpy as np
@@ -28,15 +29,27 @@ def msg_mode(request, gpu):
     gpu.set_region_mode(0, 2)
 
 
-def run(gpu, region: bytes, offs, shift: int = 0):
-    """Verify on the GPU; shift > 0 places the region `shift` bytes into its allocation."""
+def run(gpu, region: bytes, offs, shift: int = 0, workspace=None):
+    """Verify on the GPU; shift > 0 places the region `shift` bytes into its allocation. workspace: the caller's
+    (the binding has no such parameter: the C entry through lib())."""
+    import ctypes
+
     import torch
+
+    from ambry_amd._lib import check, lib
 
     buf = np.zeros(len(region) + shift, dtype=np.uint8)
     buf[shift:] = np.frombuffer(region, dtype=np.uint8)
     r = torch.from_numpy(buf).cuda()[shift:]
     o = torch.tensor(np.asarray(offs, dtype=np.int64), device="cuda")
-    status, end = gpu.verify_messages(r, o)
+    if workspace is None:
+        status, end = gpu.verify_messages(r, o)
+    else:
+        status = torch.empty(len(offs), dtype=torch.int32, device="cuda")
+        end = torch.empty(len(offs), dtype=torch.int64, device="cuda")
+        check(lib().ambrycrc_verify_messages_dev(r.data_ptr(), r.numel(), o.data_ptr(), len(offs), status.data_ptr(),
+                                                 end.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                                 ctypes.c_void_p(0)), "ambrycrc_verify_messages_dev")
     torch.cuda.synchronize()
     return status.cpu().numpy().view(np.uint32).tolist(), end.cpu().numpy().tolist()
 
@@ -52,6 +65,33 @@ def test_small_messages_unaligned_region(gpu, msg_mode, shift):
     assert st == [s for s, _ in expect]
     assert end == [e for _, e in expect]
     assert sum(1 for s in st if s) >= 40
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case(m):
+    """m small messages and the oracle's answers, shared by the three forms (build_region's first message, the
+    one with a blob of 60 KB and more, left out)."""
+    region, offs, _ = build_region(n=m + 1, seed=500 + m, corrupt_frac=0.08 if m > 1 else 0.0, big_every=10**9)
+    region, offs = region[offs[1]:], [o - offs[1] for o in offs[1:]]
+    return region, offs, [MF.verify_message(region, o) for o in offs]
+
+
+@pytest.mark.parametrize("m", [1, 409, 410])
+def test_exact_workspace_between_guards(gpu, msg_mode, m):
+    """A caller workspace of exactly ambrycrc_messages_workspace_bytes(m) between two guards, 0xA5 throughout, in
+    every verify form (a region this small fits it in region mode too): one message, and the counts on either
+    side of one plan block (5 jobs a message: 2,045 / 2,050 jobs). Status and ends as the oracle's."""
+    from test_gpu_geometry import assert_guards, guarded_workspace
+
+    region, offs, expect = exact_case(m)
+    assert len(region) <= 6144 * m
+    assert m == 1 or 20 <= sum(1 for s, _ in expect if s) <= m // 4  # refused and accepted messages both
+    whole, ws = guarded_workspace(gpu.messages_workspace_bytes(m))
+    st, end = run(gpu, region, offs, shift=13, workspace=ws)
+    assert gpu.last_message_mode(0) == MODES[msg_mode]
+    assert_guards(whole, ws)
+    assert st == [s for s, _ in expect]
+    assert end == [e for _, e in expect]
 
 
 def test_region_mode_sparse_and_overlapping_offsets(gpu, msg_mode):

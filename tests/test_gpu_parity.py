@@ -34,11 +34,11 @@ def host_u32(t):
     return t.cpu().numpy().view(np.uint32)
 
 
-def run_batch(gpu, mem_np, off, ln, crc_in=None, mem_dev=None):
+def run_batch(gpu, mem_np, off, ln, crc_in=None, mem_dev=None, workspace=None):
     torch = _torch()
     base = dev_bytes(mem_np) if mem_dev is None else mem_dev
     cin = None if crc_in is None else torch.from_numpy(np.asarray(crc_in, dtype=np.uint32).view(np.int32)).cuda()
-    out = gpu.crc32_batch(base, dev_u64(off), dev_u64(ln), crc_in=cin)
+    out = gpu.crc32_batch(base, dev_u64(off), dev_u64(ln), crc_in=cin, workspace=workspace)
     torch.cuda.synchronize()
     return host_u32(out)
 
@@ -223,6 +223,26 @@ def test_all_small_batch_garbage_workspace(gpu, oracle, with_large):
     gpu.crc32_batch(dev_bytes(mem), dev_u64(off), dev_u64(ln), crc_in=c_in, out=out, workspace=ws)
     torch.cuda.synchronize()
     assert np.array_equal(host_u32(out), oracle.batch(mem, off, ln, crc_in=cin, threads=8))
+
+
+@pytest.mark.parametrize("n", [1, 2048, 2049])
+def test_batch_exact_workspace_between_guards(gpu, oracle, n):
+    """A caller workspace of exactly ambrycrc_workspace_bytes(n) between two guards, 0xA5 throughout: one chunk,
+    and the counts on either side of one plan block (2,048 chunks). With crc_in, so the scratch's last array
+    (crc_stage) is written to its end. CRCs as the oracle's; both guards intact."""
+    from test_gpu_geometry import assert_guards, guarded_workspace
+
+    rng = np.random.default_rng(4100 + n)
+    size = 1 << 20
+    mem = stream_bytes(83, 0, size)
+    ln = rng.integers(0, 700, size=n)
+    ln[::9] = 0
+    off = rng.integers(0, size - 700, size=n)
+    cin = rng.integers(0, 1 << 32, size=n, dtype=np.uint64).astype(np.uint32)
+    whole, ws = guarded_workspace(gpu.workspace_bytes(n))
+    got = run_batch(gpu, mem, off, ln, crc_in=cin, workspace=ws)
+    assert_guards(whole, ws)
+    assert np.array_equal(got, oracle.batch(mem, off, ln, crc_in=cin))
 
 
 def test_crc_in_streaming_composition(gpu, oracle):

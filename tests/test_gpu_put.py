@@ -53,9 +53,13 @@ def _far(b, at):
 
 
 def _run(gpu, mf, msgs, out_align, field_align, gap, in_place=False, place=("key", "enckey", "props", "usermeta",
-                                                                           "blob"), far=0):
+                                                                           "blob"), far=0, workspace=None):
+    """workspace: the caller's (serialize_dev has no such parameter: the C entry through lib())."""
+    import ctypes
+
     import torch
 
+    from ambry_amd._lib import check, lib
     from ambry_amd.messages import layout, pack_batch, serialize_dev
 
     descs, fields, blobs, offs, total = pack_batch(msgs, out_align=out_align, field_align=field_align, gap=gap)
@@ -72,7 +76,13 @@ def _run(gpu, mf, msgs, out_align, field_align, gap, in_place=False, place=("key
     dev_in = (lambda b: _far(b, far)) if far else _dev
     fields_in = None if in_place and "key" in place else dev_in(fields)
     blobs_in = None if in_place and "blob" in place else dev_in(blobs)
-    serialize_dev(_dev(descs.tobytes()), out, fields_in, blobs_in, msg_len=mlen)
+    if workspace is None:
+        serialize_dev(_dev(descs.tobytes()), out, fields_in, blobs_in, msg_len=mlen)
+    else:
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        check(lib().ambrycrc_serialize_puts_dev(ptr(_dev(descs.tobytes())), len(msgs), ptr(fields_in), ptr(blobs_in),
+                                                ptr(out), ptr(mlen), ptr(workspace), workspace.numel(),
+                                                ctypes.c_void_p(0)), "ambrycrc_serialize_puts_dev")
     torch.cuda.synchronize()
     got = out.cpu().numpy().tobytes()
     exp = bytearray(b"\xAA" * total)
@@ -91,6 +101,26 @@ def _run(gpu, mf, msgs, out_align, field_align, gap, in_place=False, place=("key
 @pytest.mark.parametrize("out_align,field_align,gap", [(1, 1, 0), (16, 16, 0), (1, 7, 3), (4096, 1, 0)])
 def test_serialize_batch_copy_mode(gpu, mf, out_align, field_align, gap):
     _run(gpu, mf, random_messages(mf, 400, seed=100 + out_align + field_align), out_align, field_align, gap)
+
+
+@pytest.mark.parametrize("m", [1, 409, 410])
+def test_serialize_exact_workspace_between_guards(gpu, mf, put_form, m):
+    """A caller workspace of exactly ambrycrc_serialize_puts_workspace_bytes(m) between two guards, 0xA5
+    throughout, in both copy-mode forms (the streamed form's run slots are the workspace's last bytes): one
+    message, and the counts on either side of one plan block (5 jobs a message: 2,045 / 2,050 jobs). Small
+    fields: nearly every message short enough to stream, a few past 6 KiB, which take the job path behind `big`
+    in the same call. Output, lengths and the verify as the oracle's."""
+    from ambry_amd._lib import lib
+
+    from test_gpu_geometry import assert_guards, guarded_workspace
+
+    msgs = random_messages(mf, m, seed=600 + m, max_blob=600)
+    long = sum(len(expected(mf, x)) > 6144 for x in msgs)
+    assert long == 0 if m == 1 else 0 < long < m // 8
+    assert m == 1 or 0 < sum(x.blob_type >= 2 for x in msgs) < m  # the verify refuses some, accepts the rest
+    whole, ws = guarded_workspace(lib().ambrycrc_serialize_puts_workspace_bytes(m))
+    _run(gpu, mf, msgs, 1, 3, 0, workspace=ws)
+    assert_guards(whole, ws)
 
 
 def test_serialize_batch_in_place(gpu, mf):

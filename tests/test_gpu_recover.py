@@ -31,11 +31,11 @@ def to_numpy(out):
             status.cpu().numpy().view(np.uint32), np.frombuffer(result.cpu().numpy().tobytes(), dtype=RO.RESULT)[0])
 
 
-def run_gpu(dev, region: bytes, start=0, max_m=64, shift=0, chain=False):
+def run_gpu(dev, region: bytes, start=0, max_m=64, shift=0, chain=False, workspace=None):
     import torch
 
     rw, r = place(region, shift)
-    out = (dev.chain_messages if chain else dev.recover_messages)(r, start, max_m)
+    out = (dev.chain_messages if chain else dev.recover_messages)(r, start, max_m, workspace=workspace)
     torch.cuda.synchronize()
     assert guards_intact(rw, shift, len(region)).tobytes() == region
     return to_numpy(out)
@@ -82,6 +82,40 @@ def test_mixed_region(dev, shift):
     check(dev, dirty, 0, 400, shift)
     check(dev, dirty, doffs[150], 400, shift)
     check(dev, clean, len(clean), 4, shift)  # start == region_len: a clean empty result
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case(max_m):
+    """Small messages of every stored format, one in twenty corrupted, ten more than max_m of them, and the
+    oracle's recover and chain answers (this seed: no header among the first 410 is hit, so the chain fills
+    every slot)."""
+    import rekey_oracle as RK
+
+    region, _, _ = RK.build_region(n=max_m + 10, seed=1101, corrupt_frac=0.05, big_every=10**9, max_blob=600,
+                                   max_usermeta=300)
+    return region, RO.recover(region, 0, max_m), RO.chain_result(region, 0, max_m)
+
+
+@pytest.mark.parametrize("max_m", [1, 409, 410])
+def test_exact_workspace_between_guards(dev, max_m):
+    """Caller workspaces of exactly ambrycrc_recover_workspace_bytes and ambrycrc_chain_workspace_bytes between
+    two guards, 0xA5 throughout: one slot, and the counts on either side of one plan block of the verify
+    (5 jobs a message: 2,045 / 2,050 jobs), every slot filled. Both calls against the oracle and recover
+    against the CPU entry; the workspaces' guards intact."""
+    from test_gpu_geometry import assert_guards, guarded_workspace
+
+    region, exp, (coffs, cres) = exact_case(max_m)
+    assert exp[3]["chained"] == cres["chained"] == max_m
+    assert max_m == 1 or 10 <= sum(1 for s in exp[1] if s) <= max_m // 8  # refused and accepted messages both
+    whole, ws = guarded_workspace(dev.recover_workspace_bytes(len(region), max_m))
+    got = run_gpu(dev, region, 0, max_m, shift=5, workspace=ws)
+    assert_guards(whole, ws)
+    same_as_cpu(got, dev.recover_messages_cpu(region, 0, max_m))
+    RO.assert_call(got, exp, max_m)
+    whole, ws = guarded_workspace(dev.chain_workspace_bytes(len(region), max_m))
+    got = run_gpu(dev, region, 0, max_m, shift=5, chain=True, workspace=ws)
+    assert_guards(whole, ws)
+    assert_chain(got, coffs, cres, max_m)
 
 
 def test_reference_scenarios(dev):

@@ -42,7 +42,8 @@ def guards_intact(whole, shift: int, size: int) -> np.ndarray:
     return h[GUARD + shift:GUARD + shift + size]
 
 
-def run_gpu(messages, region: bytes, offs, descs, aux: bytes, shift=0, oshift=0, life=None, version=3, out_cap=None):
+def run_gpu(messages, region: bytes, offs, descs, aux: bytes, shift=0, oshift=0, life=None, version=3, out_cap=None,
+            workspace=None):
     """(status, out_off, out_len lists, the output view's bytes): guards checked around the region (which must
     be unchanged), aux and the output."""
     import torch
@@ -54,7 +55,8 @@ def run_gpu(messages, region: bytes, offs, descs, aux: bytes, shift=0, oshift=0,
     mo = torch.tensor(np.asarray(offs, dtype=np.uint64).view(np.int64), device="cuda")
     dd = torch.from_numpy(np.ascontiguousarray(descs).view(np.uint8).reshape(-1).copy()).cuda()
     lv = None if life is None else torch.tensor(np.asarray(life, dtype=np.int16), device="cuda")
-    _, out_off, out_len, status = messages.rekey_dev(r, mo, dd, a, header_version=version, life_version=lv, out=o)
+    _, out_off, out_len, status = messages.rekey_dev(r, mo, dd, a, header_version=version, life_version=lv, out=o,
+                                                     workspace=workspace)
     torch.cuda.synchronize()
     assert guards_intact(rw, shift, len(region)).tobytes() == region
     assert guards_intact(aw, 5, len(aux)).tobytes() == aux
@@ -95,6 +97,31 @@ def test_region_matches_oracle_and_cpu(messages, seed, shift, oshift):
         assert cst == got[0]
         for b, o, n in zip(couts, got[1], got[2]):
             assert (b or b"") == got[3][o:o + n].tobytes() if n else not b
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case(m):
+    """m small messages of every stored format, 10 % corrupted, their descriptors and the oracle's answers."""
+    region, offs, meta = RK.build_region(n=m, seed=800 + m, corrupt_frac=0.1 if m > 1 else 0.0, big_every=10**9,
+                                         max_blob=600, max_usermeta=300)
+    descs, aux = RK.build_descs(offs, meta, seed=800 + m)
+    return region, offs, descs, aux, RK.expected(region, offs, descs, aux)
+
+
+@pytest.mark.parametrize("m", [1, 512, 513])
+def test_exact_workspace_between_guards(messages, m):
+    """A caller workspace of exactly ambrycrc_rekey_workspace_bytes(m) between two guards, 0xA5 throughout: one
+    message, and the counts on either side of one plan block (4 copy jobs a message: 2,048 / 2,052 jobs).
+    Status, placement and every output byte as the oracle's; the workspace's guards intact."""
+    from test_gpu_geometry import assert_guards, guarded_workspace
+
+    region, offs, descs, aux, exp = exact_case(m)
+    if m > 1:
+        RK.assert_mix(descs, exp[0])
+    whole, ws = guarded_workspace(messages.rekey_workspace_bytes(m))
+    got = run_gpu(messages, region, offs, descs, aux, shift=13, oshift=7, workspace=ws)
+    assert_guards(whole, ws)
+    assert_outputs(got, exp)
 
 
 @pytest.mark.parametrize("version", [1, 2])

@@ -27,7 +27,7 @@ def messages(gpu):
     return M
 
 
-def run_gpu(messages, region: bytes, offs, sizes, flag, shift=0, oshift=0, out_cap=64):
+def run_gpu(messages, region: bytes, offs, sizes, flag, shift=0, oshift=0, out_cap=64, workspace=None):
     """(status list, INFO array, the output view's bytes): guards checked around the region (which must be
     unchanged) and the output."""
     import torch
@@ -36,7 +36,7 @@ def run_gpu(messages, region: bytes, offs, sizes, flag, shift=0, oshift=0, out_c
     ow, o = place(b"", oshift, out_cap)
     mo = torch.tensor(np.asarray(offs, dtype=np.uint64).view(np.int64), device="cuda")
     ms = None if sizes is None else torch.tensor(np.asarray(sizes, dtype=np.uint64).view(np.int64), device="cuda")
-    _, info, status = messages.send_messages_dev(r, mo, flag, msg_size=ms, out=o)
+    _, info, status = messages.send_messages_dev(r, mo, flag, msg_size=ms, out=o, workspace=workspace)
     torch.cuda.synchronize()
     assert guards_intact(rw, shift, len(region)).tobytes() == region
     return (status.cpu().numpy().view(np.uint32).tolist(), info.cpu().numpy().view(SO.INFO),
@@ -61,10 +61,11 @@ def assert_outputs(got, exp):
     assert (out[untouched] == 0xA5).all(), "bytes written outside the sent spans"
 
 
-def check(messages, region, offs, sizes, flag, shift=0, oshift=0, out_cap=None, cpu=False, slack=0):
-    exp = SO.expected(region, offs, sizes, flag, out_cap=out_cap)
+def check(messages, region, offs, sizes, flag, shift=0, oshift=0, out_cap=None, cpu=False, slack=0, workspace=None,
+          exp=None):
+    exp = SO.expected(region, offs, sizes, flag, out_cap=out_cap) if exp is None else exp
     cap = max(len(exp[2]) + slack, 1) if out_cap is None else out_cap  # exactly the sum of the sent spans
-    got = run_gpu(messages, region, offs, sizes, flag, shift, oshift, cap)
+    got = run_gpu(messages, region, offs, sizes, flag, shift, oshift, cap, workspace)
     assert_outputs(got, exp)
     if cpu:
         cst, cinfo, cout = SO.run_cpu(messages, region, offs, sizes, flag, out_cap=out_cap)
@@ -92,6 +93,35 @@ def test_region_matches_oracle_and_cpu(messages, flag, shift, oshift, sized):
     exp = check(messages, region, offs, sizes if sized else None, flag, shift, oshift, cpu=shift in (0, 1))
     clean, found, refused = SO.mix(exp[0], exp[1])
     assert clean >= 1 and found >= 1 and (refused >= 1 or (flag == SO.ALL and sized))
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case(m, flag):
+    """m small messages of every stored format, 10 % corrupted, their sizes, and the oracle's answers under
+    `flag`: sizes given under ALL (messages that go whole: the plain-copy scan), the headers' own otherwise."""
+    region, offs, _ = RK.build_region(n=m, seed=1000 + m, corrupt_frac=0.1 if m > 1 else 0.0, big_every=10**9,
+                                      max_blob=600, max_usermeta=300)
+    ends = offs[1:] + [len(region)]
+    sizes = [SO.header_length(region, o) or e - o for o, e in zip(offs, ends)] if flag == SO.ALL else None
+    return region, offs, sizes, SO.expected(region, offs, sizes, flag)
+
+
+@pytest.mark.parametrize("m", [1, 2048, 2049])
+@pytest.mark.parametrize("flag", [SO.ALL, SO.BLOB], ids=FLAG_NAMES.get)
+def test_exact_workspace_between_guards(messages, flag, m):
+    """A caller workspace of exactly ambrycrc_send_workspace_bytes(m) between two guards, 0xA5 throughout: one
+    message, and the counts on either side of one plan block of the per-message scans (2,048 entries). ALL
+    with given sizes runs both scans (the placement and the plain copies), BLOB reads the encryption-key
+    records first and refuses messages. Status, info and every output byte as the oracle's."""
+    from test_gpu_geometry import assert_guards, guarded_workspace
+
+    region, offs, sizes, exp = exact_case(m, flag)
+    clean, found, refused = SO.mix(exp[0], exp[1])
+    if m > 1:
+        assert clean >= 1000 and found >= 100 and (refused >= 20 or flag == SO.ALL)
+    whole, ws = guarded_workspace(messages.send_workspace_bytes(m))
+    check(messages, region, offs, sizes, flag, shift=17, oshift=5, workspace=ws, exp=exp)
+    assert_guards(whole, ws)
 
 
 SIZES = [0, 1, 15, 16, 17, 63, 64, 65, 4095, 4096, 4097, 16371, 16372, 16373, 70000, 300 * 1024]

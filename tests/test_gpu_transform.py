@@ -4,6 +4,7 @@ corrupted ones, update records and bad blob types, re-serialized at header V3, V
 every CRC recomputed. Byte-exact against oracle/message_format.py's transform_message, which
 restates ValidatingTransformer.java:46-104; outputs packed in message order; every output
 verifies clean."""
+import functools
 import struct
 import zlib
 
@@ -152,6 +153,82 @@ def test_transform_matches_oracle(gpu, mf, version):
         pos += len(exp)
     assert 0 in kinds and mf.NOT_PUT in kinds and mf.BAD_RECORD in kinds and mf.NOT_ENCODABLE in kinds
     assert len(kinds) >= 5
+
+
+def transform_in_workspace(dev, off_t, version, workspace):
+    """ambrycrc_transform_messages_dev with a caller workspace (transform_dev has no such parameter: the C entry
+    through lib()), stored life versions, the default out. Returns transform_dev's tuple."""
+    import ctypes
+
+    import torch
+
+    from ambry_amd._lib import check, lib
+    from ambry_amd.messages import out_bound
+
+    m = off_t.numel()
+    out = torch.empty(out_bound(dev.numel(), m), dtype=torch.uint8, device="cuda")
+    out_off = torch.empty(m, dtype=torch.int64, device="cuda")
+    out_len = torch.empty(m, dtype=torch.int64, device="cuda")
+    status = torch.empty(m, dtype=torch.int32, device="cuda")
+    check(lib().ambrycrc_transform_messages_dev(dev.data_ptr(), dev.numel(), off_t.data_ptr(), m, None, version,
+                                                out.data_ptr(), out.numel(), out_off.data_ptr(), out_len.data_ptr(),
+                                                status.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                                ctypes.c_void_p(0)), "ambrycrc_transform_messages_dev")
+    return out, out_off, out_len, status
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case(version, m):
+    """(region, offsets, the oracle's (status, bytes) per message) for the exact-workspace runs: at header V3 a
+    dense clean V3 region, which the fast path takes; at V2 small mixed messages (every stored format, updates,
+    flipped bits), which only the general path serves."""
+    from test_message_format import MF
+
+    if version == 3:
+        region, offs = dense_v3_region(MF, m, seed=900 + m)
+    else:
+        import rekey_oracle as RK
+
+        region, offs, _ = RK.build_region(n=m, seed=900 + m, corrupt_frac=0.1 if m > 1 else 0.0, big_every=10**9,
+                                          max_blob=600, max_usermeta=300)
+    return region, offs, [MF.transform_message(region, o, version=version) for o in offs]
+
+
+@pytest.mark.parametrize("m", [1, 409, 410])
+@pytest.mark.parametrize("version", [3, 2])
+def test_transform_exact_workspace_between_guards(gpu, version, m):
+    """A caller workspace of exactly ambrycrc_transform_workspace_bytes(m) between two guards, 0xA5 throughout:
+    one message, and the counts on either side of one plan block (5 jobs a message: 2,045 / 2,050 jobs); the
+    fast path alone (header V3 out, a region small enough for its run sums to fit the caller's workspace) and
+    the general path alone (V2 out). Status, offsets, lengths and bytes as the oracle's."""
+    import torch
+
+    from ambry_amd._lib import lib
+
+    from test_gpu_geometry import assert_guards, guarded_workspace
+
+    region, offs, expect = exact_case(version, m)
+    kinds = {st for st, _ in expect}
+    if version == 3 or m == 1:
+        assert kinds == {0}  # the fast path takes only a batch of clean messages
+    else:
+        assert 0 in kinds and len(kinds) >= 3 and 20 <= sum(1 for st, _ in expect if st) <= m // 2
+    dev = torch.frombuffer(bytearray(region), dtype=torch.uint8).cuda()
+    whole, ws = guarded_workspace(lib().ambrycrc_transform_workspace_bytes(m))
+    out, oo, ol, st = transform_in_workspace(dev, torch.tensor(offs, dtype=torch.int64, device="cuda"), version, ws)
+    torch.cuda.synchronize()
+    assert gpu.last_transform_path(0) == (1 if version == 3 else 0)
+    assert_guards(whole, ws)
+    st, oo, ol = st.cpu().numpy().view(np.uint32), oo.cpu().numpy(), ol.cpu().numpy()
+    out_h = out.cpu().numpy().tobytes()
+    pos = 0
+    for i, (exp_st, exp) in enumerate(expect):
+        assert int(st[i]) == exp_st, i
+        if exp is None:
+            assert ol[i] == 0 and oo[i] == -1
+            continue
+        assert oo[i] == pos and ol[i] == len(exp) and out_h[pos:pos + len(exp)] == exp, i
+        pos += len(exp)
 
 
 def test_transform_out_of_room(gpu, mf):
