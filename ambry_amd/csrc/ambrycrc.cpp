@@ -482,7 +482,7 @@ int enqueue_messages_parse(DevCtx* c, const uint8_t* d_region, uint64_t region_l
   a.inline_max = inline_exp ? batch_small_max(c, j) : 0;
   st->batch_ws = k.here();
   st->j = j;
-  return hip_err(desc ? launch_msg_parse_desc(a, *desc, stream) : launch_msg_parse(a, stream));
+  return hip_err(desc ? launch_msg_parse_desc(a, *desc, c->num_cu, stream) : launch_msg_parse(a, c->num_cu, stream));
 }
 
 int enqueue_messages_check(DevCtx* c, const MsgStage& st, hipStream_t stream, uint8_t* copy_dst,

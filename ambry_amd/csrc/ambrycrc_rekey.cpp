@@ -70,7 +70,7 @@ int ambrycrc_rekey_messages_dev(const uint8_t* d_region, uint64_t region_len, co
   rc = enqueue_messages_check(c, ms, stream);
   if (rc) return rc;
   // 2. refusals, output descriptors and lengths
-  if (launch_rekey_plan(a, stream) != hipSuccess) return AMBRYCRC_EHIP;
+  if (launch_rekey_plan(a, c->num_cu, stream) != hipSuccess) return AMBRYCRC_EHIP;
   // 3. packed placement: exclusive scan of the lengths, then the transform's place step (NO_ROOM
   //    for a message past out_cap, which still advances the running offset)
   const PlanArgs p = plan_scan_args(d_msg_off, d_out_len, m, shared, w.scan_out);
@@ -88,7 +88,7 @@ int ambrycrc_rekey_messages_dev(const uint8_t* d_region, uint64_t region_len, co
   //    then header, record heads, properties and every trailer
   rc = enqueue_batch(c, a.aux, a.cjob_off, a.cjob_len, nullptr, w.ccrc, m, shared, stream);
   if (rc) return rc;
-  if (launch_rekey_write(a, stream) != hipSuccess) return AMBRYCRC_EHIP;
+  if (launch_rekey_write(a, c->num_cu, stream) != hipSuccess) return AMBRYCRC_EHIP;
   // 5. the bodies, balanced by cost over the whole grid
   return enqueue_scan_copy(c, a.cp_src, a.cp_dst, a.cp_len, a.cp_cost, j, d_out, shared, w.cp_scan_out, nullptr, stream);
 }

@@ -70,10 +70,10 @@ int ambrycrc_send_messages_dev(const uint8_t* d_region, uint64_t region_len, con
   if (!whole_copies) a.g_src = nullptr;
   const PlanArgs p = plan_scan_args(d_msg_off, a.len, m, ms.batch_ws, w.scan_out);
   a.start = p.byte_start;
-  if (launch_send_plan(a, stream) != hipSuccess) return AMBRYCRC_EHIP;
+  if (launch_send_plan(a, c->num_cu, stream) != hipSuccess) return AMBRYCRC_EHIP;
   // 4. packed placement: exclusive scan of the span lengths, then every job's destination
   if (launch_plan(p, stream) != hipSuccess) return AMBRYCRC_EHIP;
-  if (launch_send_jobs(a, stream) != hipSuccess) return AMBRYCRC_EHIP;
+  if (launch_send_jobs(a, c->num_cu, stream) != hipSuccess) return AMBRYCRC_EHIP;
   // 5. the verify's CRC pass as a copy-through: every sent record read once, hashed and written
   rc = enqueue_messages_check(c, ms, stream, d_out, a.copy_off);
   if (rc) return rc;
@@ -83,7 +83,7 @@ int ambrycrc_send_messages_dev(const uint8_t* d_region, uint64_t region_len, con
     if (rc) return rc;
   }
   // 7. the final check bits, the trailers, and under ALL the headers and store keys
-  return hip_err(launch_send_finish(a, stream));
+  return hip_err(launch_send_finish(a, c->num_cu, stream));
 }
 
 }  // extern "C"

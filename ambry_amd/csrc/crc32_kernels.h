@@ -329,7 +329,7 @@ struct TransformArgs {
 hipError_t launch_transform_desc(const TransformArgs& a, hipStream_t s);
 // msg_parse_kernel fused with transform_desc_kernel (the speculative pass): a and t describe the
 // same messages.
-hipError_t launch_msg_parse_desc(const MsgArgs& a, const TransformArgs& t, hipStream_t s);
+hipError_t launch_msg_parse_desc(const MsgArgs& a, const TransformArgs& t, int num_cu, hipStream_t s);
 hipError_t launch_transform_place(const TransformArgs& a, const uint64_t* start, hipStream_t s);
 hipError_t launch_transform_jobs(const TransformArgs& a, hipStream_t s);
 hipError_t launch_transform_finish(const TransformArgs& a, hipStream_t s);
@@ -372,8 +372,8 @@ struct RekeyArgs {
   uint64_t* cp_cost;
   const uint32_t* img;
 };
-hipError_t launch_rekey_plan(const RekeyArgs& a, hipStream_t s);
-hipError_t launch_rekey_write(const RekeyArgs& a, hipStream_t s);
+hipError_t launch_rekey_plan(const RekeyArgs& a, int num_cu, hipStream_t s);
+hipError_t launch_rekey_write(const RekeyArgs& a, int num_cu, hipStream_t s);
 
 // MessageFormatSend (send_kernels.hip, ambrycrc_send.cpp; the per-message rules: send.h): the verify's
 // parse, the encryption-key records' CRCs, then one thread per message decides what is sent and what
@@ -410,9 +410,9 @@ struct SendArgs {
   uint64_t* g_len;
   uint64_t* g_cost;
 };
-hipError_t launch_send_plan(const SendArgs& a, hipStream_t s);
-hipError_t launch_send_jobs(const SendArgs& a, hipStream_t s);
-hipError_t launch_send_finish(const SendArgs& a, hipStream_t s);
+hipError_t launch_send_plan(const SendArgs& a, int num_cu, hipStream_t s);
+hipError_t launch_send_jobs(const SendArgs& a, int num_cu, hipStream_t s);
+hipError_t launch_send_finish(const SendArgs& a, int num_cu, hipStream_t s);
 
 // ---- copy-mode serialization of small messages by streaming the output (round 6)
 // put_stream_kernel: a wave per message writes the whole message -- header and record heads computed,
@@ -446,7 +446,7 @@ hipError_t launch_gather_copy(const CopyArgs& a, int grid, hipStream_t s);
 hipError_t launch_trailer_parse(const TrailerArgs& a, hipStream_t s);
 hipError_t launch_trailer_verify(const TrailerArgs& a, hipStream_t s);
 
-hipError_t launch_msg_parse(const MsgArgs& a, hipStream_t s);
+hipError_t launch_msg_parse(const MsgArgs& a, int num_cu, hipStream_t s);
 // Region mode, pass 2: parse, record CRCs from the run sums, status (a.job_* / expected / crc unused).
 hipError_t launch_region_msg(const MsgArgs& a, const RegionArgs& g, int num_cu, hipStream_t s);
 // Region mode, after pass 2 (or the one-pass tail): the long records of g.lng, split over the whole

@@ -33,6 +33,7 @@
 #include "crc_img.h"
 #include "put_layout.h"
 #include "region_proc.h"
+#include "wave_tools.h"
 
 // A/B knob: s_setprio 3 around the streamed group path's loads, as the wave-mode body has it.
 
@@ -65,6 +66,22 @@ __device__ __forceinline__ void fill_lds(const uint32_t* __restrict__ img) {
 constexpr uint32_t kRunsBufBytes = 1024;
 __shared__ __attribute__((aligned(16))) uint32_t g_lds_runs[(kSliceBytes + 16 * kRunsBufBytes) / 4];
 
+// LDS-DMA of the slice tables (image bytes [0, 128 KiB)) into g_lds_runs, as fill_lds. The issue
+// half alone is for a kernel that stages more before its one wait (region_fused_kernel).
+__device__ __forceinline__ void issue_lds_slices(const uint32_t* __restrict__ img) {
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  for (uint32_t c = wv; c < kSliceBytes / 1024; c += nw)
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) void*)(reinterpret_cast<const uint8_t*>(img) + c * 1024 + lane * 16),
+        (__attribute__((address_space(3))) void*)(reinterpret_cast<uint8_t*>(g_lds_runs) + c * 1024), 16, 0, 0);
+}
+
+__device__ __forceinline__ void fill_lds_slices(const uint32_t* __restrict__ img) {
+  issue_lds_slices(img);
+  __builtin_amdgcn_s_waitcnt(0);
+  __syncthreads();
+}
+
 // W = 0: the full image (g_lds); W = 1: the slice tables of region_runs_kernel (g_lds_runs).
 template <int W = 0>
 __device__ __forceinline__ uint32_t lds_rd(uint32_t byte_addr) {
@@ -89,12 +106,6 @@ __device__ __forceinline__ uint32_t tree_partner(uint32_t v) {
   if constexpr (LVL < 4) return dpp<0x110 + (1 << LVL), 0xf>(v);
   else if constexpr (LVL == 4) return dpp<0x142, 0xa>(v);
   else return dpp<0x143, 0xc>(v);
-}
-
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, uint32_t lane) {
-  const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, lane);
-  const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), lane);
-  return ((uint64_t)hi << 32) | lo;
 }
 
 // Per-lane address constants for slice table j: region bit, (j&1)*128, lane column.
@@ -1050,24 +1061,6 @@ __device__ __forceinline__ void group_phase_cls(const SweepArgs& a, uint32_t wav
   group_class_t4s<16, 3, NT, COPY>(a, c3, c4, wave, nwaves, lane, k);
 }
 
-// Largest c in [0, n) with byte_start[c] <= g (byte_start nondecreasing, byte_start[0] = 0).
-// 64-ary search: one coalesced probe per lane per round, log64(n) rounds.
-__device__ __forceinline__ uint32_t find_chunk(const uint64_t* __restrict__ byte_start, uint32_t n, uint64_t g,
-                                               uint32_t lane) {
-  uint32_t lo = 0, hi = n;  // invariant: byte_start[lo] <= g, answer in [lo, hi)
-  while (hi - lo > 1) {
-    const uint32_t step = (hi - lo + 63) / 64;
-    const uint32_t idx = lo + lane * step;
-    const bool ok = idx < hi && byte_start[idx] <= g;
-    const uint64_t m = __ballot(ok);
-    const uint32_t last = 63u - (uint32_t)__builtin_clzll(m);
-    const uint32_t nhi = lo + (last + 1) * step;
-    lo = lo + last * step;
-    hi = nhi < hi ? nhi : hi;
-  }
-  return lo;
-}
-
 // Chunk-relative cut for global stream position g inside chunk c (0 < r < len):
 // snapped so the memory address is 16-B aligned. Pure function of (g, chunk), so the
 // two waves meeting at g agree on it.
@@ -1182,7 +1175,7 @@ __global__ __launch_bounds__(1024) void crc32_sweep_kernel(SweepArgs a) {
   };
 
   for (;;) {
-    uint32_t c = __builtin_amdgcn_readfirstlane(find_chunk(a.byte_start, a.n, g0, lane));
+    uint32_t c = __builtin_amdgcn_readfirstlane(find_start(a.byte_start, a.n, g0, lane));
     // Descriptors fetched 64 at a time (lane j <- chunk c+j), read back with readlane:
     // one load round trip per 64 chunks. byte_start only seeds a scalar running sum, so
     // 5 VGPRs stay live across the body.
@@ -1229,7 +1222,7 @@ __global__ __launch_bounds__(1024) void crc32_sweep_kernel(SweepArgs a) {
       // instead of walking it 64 descriptors at a time.
       uint32_t next = c + cnt;
       if (!work && !done && next < a.n) {
-        const uint32_t far = __builtin_amdgcn_readfirstlane(find_chunk(a.byte_start, a.n, bsc, lane));
+        const uint32_t far = __builtin_amdgcn_readfirstlane(find_start(a.byte_start, a.n, bsc, lane));
         next = far > next ? far : next;
       }
       c = next;
@@ -1502,12 +1495,10 @@ __global__ void fill_splitmix_kernel(uint8_t* __restrict__ dst, uint64_t nbytes,
 
 // ---------------------------------------------------------------- launchers
 hipError_t launch_plan(const PlanArgs& a, hipStream_t s) {
-  const uint32_t blocks = (a.n + kPlanPerBlock - 1) / kPlanPerBlock;
-  if (blocks == 0) return hipSuccess;
+  const uint32_t blocks = blocks_for(a.n, 0, 0, kPlanPerBlock);
   // one planning block needs no per-block sums (its carry is 0)
   if (blocks > 1) hipLaunchKernelGGL(crc32_plan_count_kernel, dim3(blocks), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(crc32_plan_scan_kernel, dim3(blocks), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(crc32_plan_scan_kernel, blocks, 256, s, a);
 }
 
 hipError_t launch_sweep_copy(const SweepArgs& a, int grid, int num_cu, int variant, hipStream_t s) {
@@ -1566,15 +1557,7 @@ __global__ __launch_bounds__(1024) void region_runs_kernel(RegionArgs a) {
   const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
   // Shares wave-major over workgroups, as the sweep kernel's (CU-major shares measured the same).
   const uint32_t wave = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) * gridDim.x + blockIdx.x);
-  {  // LDS-DMA of the slice tables (image bytes [0, 128 KiB)), as fill_lds
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    for (uint32_t c = wv; c < kSliceBytes / 1024; c += nw)
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(reinterpret_cast<const uint8_t*>(a.img) + c * 1024 + lane * 16),
-          (__attribute__((address_space(3))) void*)(reinterpret_cast<uint8_t*>(g_lds_runs) + c * 1024), 16, 0, 0);
-    __builtin_amdgcn_s_waitcnt(0);
-    __syncthreads();
-  }
+  fill_lds_slices(a.img);
   const uint32_t lane = threadIdx.x & 63u;
   const LaneConst k = make_lane_const(lane);
   // Groups of four super-blocks: contiguous shares (wave w: [s0, s1) in steps of 4), or with
@@ -1640,9 +1623,7 @@ __global__ __launch_bounds__(1024) void region_runs_kernel(RegionArgs a) {
 }
 
 hipError_t launch_region_runs(const RegionArgs& a, int grid, hipStream_t s) {
-  if (a.nsb == 0) return hipSuccess;
-  hipLaunchKernelGGL(region_runs_kernel, dim3(grid), dim3(1024), 0, s, a);
-  return hipGetLastError();
+  return launch_items(region_runs_kernel, a.nsb ? (uint32_t)grid : 0u, 1024, s, a);
 }
 
 // ---- copy-mode serialization of small messages (put_stream_kernel; StreamPutArgs, crc32_kernels.h) ----
@@ -1744,15 +1725,7 @@ struct StreamUnit {  // wave-uniform: one message's output and its run slots
 }  // namespace
 
 __global__ __launch_bounds__(1024) void put_stream_kernel(StreamPutArgs a) {
-  {  // LDS-DMA of the slice tables (image bytes [0, 128 KiB)), as region_runs_kernel
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    for (uint32_t c = wv; c < kSliceBytes / 1024; c += nw)
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(reinterpret_cast<const uint8_t*>(a.img) + c * 1024 + lane * 16),
-          (__attribute__((address_space(3))) void*)(reinterpret_cast<uint8_t*>(g_lds_runs) + c * 1024), 16, 0, 0);
-    __builtin_amdgcn_s_waitcnt(0);
-    __syncthreads();
-  }
+  fill_lds_slices(a.img);
   const uint32_t lane = threadIdx.x & 63u;
   const LaneConst k = make_lane_const(lane);
   uint32_t* buf = g_lds_runs + kSliceBytes / 4 + (threadIdx.x >> 6) * (kRunsBufBytes / 4);
@@ -1874,15 +1847,7 @@ __global__ __launch_bounds__(1024) void put_stream_kernel(StreamPutArgs a) {
 }
 #else
 __global__ __launch_bounds__(1024) void put_stream_kernel(StreamPutArgs a) {
-  {  // LDS-DMA of the slice tables (image bytes [0, 128 KiB)), as region_runs_kernel
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    for (uint32_t c = wv; c < kSliceBytes / 1024; c += nw)
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(reinterpret_cast<const uint8_t*>(a.img) + c * 1024 + lane * 16),
-          (__attribute__((address_space(3))) void*)(reinterpret_cast<uint8_t*>(g_lds_runs) + c * 1024), 16, 0, 0);
-    __builtin_amdgcn_s_waitcnt(0);
-    __syncthreads();
-  }
+  fill_lds_slices(a.img);
   const uint32_t lane = threadIdx.x & 63u;
   const LaneConst k = make_lane_const(lane);
   uint32_t* buf = g_lds_runs + kSliceBytes / 4 + (threadIdx.x >> 6) * (kRunsBufBytes / 4);
@@ -1957,9 +1922,7 @@ __global__ __launch_bounds__(1024) void put_stream_kernel(StreamPutArgs a) {
 #endif  // AMBRY_STREAM_PIPE
 
 hipError_t launch_put_stream(const StreamPutArgs& a, int num_cu, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(put_stream_kernel, dim3((uint32_t)num_cu), dim3(1024), 0, s, a);
-  return hipGetLastError();
+  return launch_items(put_stream_kernel, a.m ? (uint32_t)num_cu : 0u, 1024, s, a);
 }
 
 size_t stream_put_rk_bytes(size_t m) { return ((kRunPad + (size_t)m * kStreamPutRuns) * sizeof(uint32_t) + 255) & ~size_t(255); }
@@ -1977,15 +1940,6 @@ size_t stream_put_rk_bytes(size_t m) { return ((kRunPad + (size_t)m * kStreamPut
 // streamed, then until its messages' ends are; then region::process_message. A message that
 // starts before the share or ends past it goes to the deferred list for region_tail_kernel.
 // Offsets out of order anywhere set ctl[0], and the tail kernel then redoes every message.
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint64_t w = __shfl_xor(v, o);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-
 // Base-relative position of message i's start (past the region: its end).
 __device__ __forceinline__ uint64_t msg_pos(const FusedArgs& f, uint64_t i) {
   const uint64_t o = f.a.msg_off[i];
@@ -2022,12 +1976,7 @@ __global__ __launch_bounds__(64 * W) void region_fused_kernel(FusedArgs f) {
   __shared__ uint32_t dn[region::kDirSets * region::kNibWords];
   __shared__ uint32_t done[16];
   {  // LDS-DMA of the slice tables (the streamers'), then the processors' compact tables and nibble sets
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    for (uint32_t c = wv; c < kSliceBytes / 1024; c += nw)
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(reinterpret_cast<const uint8_t*>(f.g.img) + c * 1024 +
-                                                          lane * 16),
-          (__attribute__((address_space(3))) void*)(reinterpret_cast<uint8_t*>(g_lds_runs) + c * 1024), 16, 0, 0);
+    issue_lds_slices(f.g.img);
     for (uint32_t i = threadIdx.x; i < 1024; i += blockDim.x) {
       const uint32_t j = i >> 8, b = i & 255u;
       tbl[i] = f.g.img[(((j >> 1) << 16) | (b << 8) | ((j & 1) << 7)) >> 2];
@@ -2282,18 +2231,15 @@ hipError_t launch_region_fused(const FusedArgs& f, int num_cu, hipStream_t s) {
   // A wave per deferred message whenever there are at most 4 per CU (~1 per share boundary, each
   // maybe a 4 MiB message whose records a lane alone would walk for milliseconds): blocks without a
   // message return before staging their tables.
-  uint64_t blocks = (f.a.m + 3) / 4;
-  if (blocks > (uint64_t)num_cu * 4) blocks = (uint64_t)num_cu * 4;
-  if (copy) hipLaunchKernelGGL(region_tail_kernel<true>, dim3((uint32_t)blocks), dim3(256), 0, s, f);
-  else hipLaunchKernelGGL(region_tail_kernel<false>, dim3((uint32_t)blocks), dim3(256), 0, s, f);
+  const uint32_t blocks = blocks_for(f.a.m, num_cu, 4, 4);
+  if (copy) hipLaunchKernelGGL(region_tail_kernel<true>, dim3(blocks), dim3(256), 0, s, f);
+  else hipLaunchKernelGGL(region_tail_kernel<false>, dim3(blocks), dim3(256), 0, s, f);
   if (!copy && f.g.lng.ctr) {  // the long records the tail listed, over the whole grid
     const hipError_t e = launch_region_long(f.a, f.g, num_cu, s);
     if (e != hipSuccess) return e;
   }
   if (copy && (f.life || f.path_out)) {
-    uint64_t pb = f.life ? (f.a.m + 255) / 256 : 1;
-    if (pb > (uint64_t)num_cu * 8) pb = (uint64_t)num_cu * 8;
-    hipLaunchKernelGGL(region_patch_kernel, dim3((uint32_t)pb), dim3(256), 0, s, f);
+    hipLaunchKernelGGL(region_patch_kernel, dim3(f.life ? blocks_for(f.a.m, num_cu, 8) : 1u), dim3(256), 0, s, f);
   }
   return hipGetLastError();
 }
@@ -2329,9 +2275,7 @@ hipError_t launch_sweep(const SweepArgs& a, int grid, int num_cu, int variant, h
 
 hipError_t launch_verify(const uint32_t* crc, const uint32_t* expected, uint8_t* mismatch, uint32_t* count,
                          uint32_t n, hipStream_t s) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(crc32_verify_kernel, dim3((n + 255) / 256), dim3(256), 0, s, crc, expected, mismatch, count, n);
-  return hipGetLastError();
+  return launch_items(crc32_verify_kernel, blocks_for(n), 256, s, crc, expected, mismatch, count, n);
 }
 
 hipError_t launch_fill(uint8_t* dst, uint64_t nbytes, uint64_t seed, uint64_t stream_off, hipStream_t s) {

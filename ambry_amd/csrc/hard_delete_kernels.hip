@@ -23,6 +23,7 @@
 #include "crc_img.h"
 #include "hard_delete.h"
 #include "msg_parse.h"
+#include "wave_tools.h"
 
 namespace ambrycrc {
 
@@ -188,29 +189,6 @@ __global__ __launch_bounds__(256) void hd_seal_kernel(HdArgs a) {
 }
 
 // ---------------------------------------------------------------- zero fill
-// rl64 and find_job as gather_copy_kernel's (put_kernels.hip keeps them file-local).
-__device__ __forceinline__ uint64_t hd_rl64(uint64_t v, uint32_t lane) {
-  const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, lane);
-  const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), lane);
-  return ((uint64_t)hi << 32) | lo;
-}
-
-// Largest c in [0, n) with start[c] <= g (start nondecreasing, start[0] = 0): 64-ary search.
-__device__ __forceinline__ uint32_t hd_find_job(const uint64_t* __restrict__ start, uint32_t n, uint64_t g,
-                                                uint32_t lane) {
-  uint32_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const uint32_t step = (hi - lo + 63) / 64;
-    const uint32_t idx = lo + lane * step;
-    const uint64_t m = __ballot(idx < hi && start[idx] <= g);
-    const uint32_t last = 63u - (uint32_t)__builtin_clzll(m);
-    const uint32_t nhi = lo + (last + 1) * step;
-    lo = lo + last * step;
-    hi = nhi < hi ? nhi : hi;
-  }
-  return lo;
-}
-
 // One wave zeroes [dst, dst + n) (wave-uniform arguments): single bytes up to 16-B alignment, the body
 // as 16-B stores, lane-strided (1 KiB per wave store), four per lane in flight, then the tail bytes.
 // Nothing is read. Plain stores: nontemporal ones measured slower here (1,024 x 4 MiB blobs 1.005 ms a
@@ -235,67 +213,27 @@ __device__ __forceinline__ void fill_range(uint8_t* __restrict__ dst, uint64_t n
   if (lane < t) d1[16 * n16 + lane] = 0;
 }
 
-// Persistent, cost-balanced, as gather_copy_kernel: wave w takes [w*S, (w+1)*S) of the jobs'
-// concatenated costs (start = exclusive scan of len + kCopyJobCost); job j's bytes are the first
-// len[j] units of its cost range, so every byte is zeroed by exactly one wave. Descriptors 64 at a
-// time, broadcast by readlane; control flow is wave-uniform; no atomics, no hand-off.
+// Persistent, cost-balanced zero fill of the jobs' bytes (cost_share_walk, wave_tools.h).
 __global__ __launch_bounds__(256) void hd_fill_kernel(HdFillArgs a) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
   const uint32_t wave = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) * gridDim.x + blockIdx.x);
-  const uint64_t total = a.start[a.n];
-  uint64_t S = (total + nwaves - 1) / nwaves;
-  S = (S + 255) & ~uint64_t(255);
-  S = S < 4096 ? 4096 : S;
-  const uint64_t g0 = (uint64_t)wave * S;
-  if (g0 >= total) return;
-  const uint64_t g1 = g0 + S < total ? g0 + S : total;
-  uint32_t c = __builtin_amdgcn_readfirstlane(hd_find_job(a.start, a.n, g0, lane));
-  while (c < a.n) {
-    const uint32_t cnt = a.n - c < 64u ? a.n - c : 64u;
-    uint64_t w_st = ~0ull, w_len = 0, w_dst = 0;
-    if (lane < cnt) {
-      w_st = a.start[c + lane];
-      w_len = a.len[c + lane];
-      w_dst = a.dst_off[c + lane];
-    }
-    bool work = false;
-    for (uint32_t j = 0; j < cnt; ++j) {
-      const uint64_t st = hd_rl64(w_st, j);
-      if (st >= g1) return;
-      const uint64_t len = hd_rl64(w_len, j);
-      if (len == 0) continue;
-      work = true;
-      const uint64_t r0 = g0 > st ? g0 - st : 0;
-      const uint64_t r1 = g1 - st < len ? g1 - st : len;
-      if (r0 < r1) fill_range(a.dst + hd_rl64(w_dst, j) + r0, r1 - r0, lane);
-    }
-    // a window of empty jobs (refused messages: cost 0, all at one start): jump to the run's end
-    uint32_t next = c + cnt;
-    if (!work && next < a.n) {
-      const uint32_t far = __builtin_amdgcn_readfirstlane(hd_find_job(a.start, a.n, hd_rl64(w_st, cnt - 1), lane));
-      next = far > next ? far : next;
-    }
-    c = next;
-  }
+  uint64_t w_dst = 0;
+  cost_share_walk(
+      a.start, a.len, a.n, wave, nwaves, lane, [&](uint32_t i) { w_dst = a.dst_off[i]; },
+      [&](uint32_t j, uint64_t r0, uint64_t n) { fill_range(a.dst + readlane64(w_dst, j) + r0, n, lane); });
 }
 
 hipError_t launch_hd_parse(const HdArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(hd_parse_kernel, dim3((uint32_t)((a.m + 255) / 256)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(hd_parse_kernel, blocks_for(a.m), 256, s, a);
 }
 
 hipError_t launch_hd_seal(const HdArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(hd_seal_kernel, dim3((uint32_t)((a.m + 255) / 256)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(hd_seal_kernel, blocks_for(a.m), 256, s, a);
 }
 
 hipError_t launch_hd_fill(const HdFillArgs& a, int grid, hipStream_t s) {
-  if (a.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(hd_fill_kernel, dim3(grid), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(hd_fill_kernel, a.n ? (uint32_t)grid : 0u, 256, s, a);
 }
 
 }  // namespace ambrycrc

@@ -25,6 +25,7 @@
 #include "msg_parse.h"
 #include "record_fields.h"
 #include "region_crc.h"
+#include "wave_tools.h"
 
 namespace ambrycrc {
 
@@ -68,16 +69,6 @@ __global__ __launch_bounds__(256) void msg_parse_kernel(MsgArgs a, TransformArgs
     if (a.msg_end) a.msg_end[i] = r.end ? off + r.end : 0;
     if constexpr (DESC) transform_describe(t, i, r.status, pf_ok ? &pf : nullptr);
   }
-}
-
-static uint32_t parse_blocks(uint64_t m) {
-  uint64_t blocks = (m + 255) / 256;
-  int dev = 0, cu = 0;
-  if (AMBRY_PARSE_BPC > 0 && hipGetDevice(&dev) == hipSuccess &&
-      hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cu > 0 &&
-      blocks > (uint64_t)cu * AMBRY_PARSE_BPC)
-    blocks = (uint64_t)cu * AMBRY_PARSE_BPC;
-  return (uint32_t)blocks;
 }
 
 // Region mode, pass 2: one thread per message parses it as msg_parse_kernel does
@@ -498,69 +489,49 @@ __global__ void xform_signal_kernel(const uint32_t* xfail, uint32_t* done, uint3
 }
 
 hipError_t launch_xform_signal(const uint32_t* xfail, uint32_t* done, uint32_t seq, hipStream_t s) {
-  hipLaunchKernelGGL(xform_signal_kernel, dim3(1), dim3(64), 0, s, xfail, done, seq);
-  return hipGetLastError();
+  return launch_items(xform_signal_kernel, 1, 64, s, xfail, done, seq);
 }
 
 hipError_t launch_transform_jobs(const TransformArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(transform_jobs_kernel, dim3((uint32_t)((a.m + 255) / 256)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(transform_jobs_kernel, blocks_for(a.m), 256, s, a);
 }
 
 hipError_t launch_transform_finish(const TransformArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(transform_finish_kernel, dim3((uint32_t)((a.m + 255) / 256)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(transform_finish_kernel, blocks_for(a.m), 256, s, a);
 }
 
 hipError_t launch_transform_merge(const TransformArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(transform_merge_kernel, dim3((uint32_t)((a.m + 255) / 256)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(transform_merge_kernel, blocks_for(a.m), 256, s, a);
 }
 
 hipError_t launch_props_fix(const TransformArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(props_fix_kernel, dim3((uint32_t)((a.m + 255) / 256)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(props_fix_kernel, blocks_for(a.m), 256, s, a);
 }
 
 hipError_t launch_transform_desc(const TransformArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(transform_desc_kernel, dim3((uint32_t)((a.m + 255) / 256)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(transform_desc_kernel, blocks_for(a.m), 256, s, a);
 }
 
 hipError_t launch_transform_place(const TransformArgs& a, const uint64_t* start, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(transform_place_kernel, dim3((uint32_t)((a.m + 255) / 256)), dim3(256), 0, s, a, start);
-  return hipGetLastError();
+  return launch_items(transform_place_kernel, blocks_for(a.m), 256, s, a, start);
 }
 
 hipError_t launch_trailer_parse(const TrailerArgs& a, hipStream_t s) {
-  if (a.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(trailer_parse_kernel, dim3((uint32_t)((a.n + 255) / 256)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(trailer_parse_kernel, blocks_for(a.n), 256, s, a);
 }
 
 hipError_t launch_trailer_verify(const TrailerArgs& a, hipStream_t s) {
-  if (a.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(trailer_verify_kernel, dim3((uint32_t)((a.n + 255) / 256)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(trailer_verify_kernel, blocks_for(a.n), 256, s, a);
 }
 
-hipError_t launch_msg_parse(const MsgArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(msg_parse_kernel<false>, dim3(parse_blocks(a.m)), dim3(256), 0, s, a, TransformArgs{});
-  return hipGetLastError();
+hipError_t launch_msg_parse(const MsgArgs& a, int num_cu, hipStream_t s) {
+  return launch_items(msg_parse_kernel<false>, blocks_for(a.m, num_cu, AMBRY_PARSE_BPC), 256, s, a, TransformArgs{});
 }
 
-hipError_t launch_msg_parse_desc(const MsgArgs& a, const TransformArgs& t, hipStream_t s) {
+hipError_t launch_msg_parse_desc(const MsgArgs& a, const TransformArgs& t, int num_cu, hipStream_t s) {
   if (a.m == 0) return hipSuccess;
   if (t.m != a.m || t.region != a.region || t.msg_off != a.msg_off) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(msg_parse_kernel<true>, dim3(parse_blocks(a.m)), dim3(256), 0, s, a, t);
-  return hipGetLastError();
+  return launch_items(msg_parse_kernel<true>, blocks_for(a.m, num_cu, AMBRY_PARSE_BPC), 256, s, a, t);
 }
 
 // Blocks per CU by message size (one box, ms per call, two interleaved runs; the
@@ -570,12 +541,8 @@ hipError_t launch_msg_parse_desc(const MsgArgs& a, const TransformArgs& t, hipSt
 // message take AMBRY_REGION_BPC_SMALL blocks per CU.
 constexpr uint64_t kRegionSmallPerMessage = 1536;
 hipError_t launch_region_msg(const MsgArgs& a, const RegionArgs& g, int num_cu, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  const uint64_t bpc = a.region_len <= kRegionSmallPerMessage * a.m ? AMBRY_REGION_BPC_SMALL : AMBRY_REGION_BPC;
-  uint64_t blocks = (a.m + 255) / 256;
-  if (bpc > 0 && blocks > (uint64_t)num_cu * bpc) blocks = (uint64_t)num_cu * bpc;
-  hipLaunchKernelGGL(region_msg_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, a, g);
-  return hipGetLastError();
+  const uint32_t bpc = a.region_len <= kRegionSmallPerMessage * a.m ? AMBRY_REGION_BPC_SMALL : AMBRY_REGION_BPC;
+  return launch_items(region_msg_kernel, blocks_for(a.m, num_cu, bpc), 256, s, a, g);
 }
 
 // The long records the region kernels listed (LongList), piece by piece: wave w hashes pieces w,
@@ -697,15 +664,11 @@ __global__ __launch_bounds__(256) void region_long_kernel(MsgArgs a, RegionArgs 
 }
 
 hipError_t launch_region_long(const MsgArgs& a, const RegionArgs& g, int num_cu, hipStream_t s) {
-  if (a.m == 0 || !g.lng.ctr) return hipSuccess;
-  hipLaunchKernelGGL(region_long_kernel, dim3((uint32_t)num_cu * 2), dim3(256), 0, s, a, g);
-  return hipGetLastError();
+  return launch_items(region_long_kernel, a.m && g.lng.ctr ? (uint32_t)num_cu * 2 : 0u, 256, s, a, g);
 }
 
 hipError_t launch_msg_reduce(const MsgArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(msg_reduce_kernel, dim3((uint32_t)((a.m + 255) / 256)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(msg_reduce_kernel, blocks_for(a.m), 256, s, a);
 }
 
 }  // namespace ambrycrc

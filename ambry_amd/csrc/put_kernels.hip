@@ -19,6 +19,7 @@
 #include "put_layout.h"
 #include "record_fields.h"
 #include "region_crc.h"
+#include "wave_tools.h"
 
 namespace ambrycrc {
 
@@ -176,36 +177,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(AMBRY_REGIO
 }
 
 hipError_t launch_put_stream_seal(const StreamPutArgs& a, int num_cu, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  uint64_t blocks = (a.m + 255) / 256;
-  if (blocks > (uint64_t)num_cu * AMBRY_SEAL_BPC) blocks = (uint64_t)num_cu * AMBRY_SEAL_BPC;
-  hipLaunchKernelGGL(put_stream_seal_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(put_stream_seal_kernel, blocks_for(a.m, num_cu, AMBRY_SEAL_BPC), 256, s, a);
 }
 
 // ---------------------------------------------------------------- gather copy
-__device__ __forceinline__ uint64_t rl64(uint64_t v, uint32_t lane) {
-  const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, lane);
-  const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), lane);
-  return ((uint64_t)hi << 32) | lo;
-}
-
-// Largest c in [0, n) with start[c] <= g (start nondecreasing, start[0] = 0): 64-ary search.
-__device__ __forceinline__ uint32_t find_job(const uint64_t* __restrict__ start, uint32_t n, uint64_t g,
-                                             uint32_t lane) {
-  uint32_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const uint32_t step = (hi - lo + 63) / 64;
-    const uint32_t idx = lo + lane * step;
-    const uint64_t m = __ballot(idx < hi && start[idx] <= g);
-    const uint32_t last = 63u - (uint32_t)__builtin_clzll(m);
-    const uint32_t nhi = lo + (last + 1) * step;
-    lo = lo + last * step;
-    hi = nhi < hi ? nhi : hi;
-  }
-  return lo;
-}
-
 // Dword k of bytes [4Q + r, 4Q + r + 16) of the 32-byte concatenation a||b (little endian).
 template <int Q>
 __device__ __forceinline__ u32x4p shift_pair(const u32x4p& a, const u32x4p& b, uint32_t r) {
@@ -276,71 +251,36 @@ __device__ __forceinline__ void copy_range(uint8_t* __restrict__ dst, const uint
   if (lane < t) d1[16 * n16 + lane] = s1[16 * n16 + lane];
 }
 
-// Persistent, cost-balanced: wave w takes [w*S, (w+1)*S) of the jobs' concatenated costs (start =
-// exclusive scan of len + kCopyJobCost, from the plan kernel); job j's bytes are the first len[j]
-// units of its cost range, so every byte is copied by exactly one wave. Descriptors 64 at a time.
+// Persistent, cost-balanced copy of the jobs' bytes (cost_share_walk, wave_tools.h; start is the
+// plan kernel's exclusive scan of len + kCopyJobCost).
 __global__ __launch_bounds__(256) void gather_copy_kernel(CopyArgs a) {
   if (a.gate && *a.gate == 0) return;  // uniform
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
   const uint32_t wave = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) * gridDim.x + blockIdx.x);
-  const uint64_t total = a.start[a.n];
-  uint64_t S = (total + nwaves - 1) / nwaves;
-  S = (S + 255) & ~uint64_t(255);
-  S = S < 4096 ? 4096 : S;
-  const uint64_t g0 = (uint64_t)wave * S;
-  if (g0 >= total) return;
-  const uint64_t g1 = g0 + S < total ? g0 + S : total;
-  uint32_t c = __builtin_amdgcn_readfirstlane(find_job(a.start, a.n, g0, lane));
-  while (c < a.n) {
-    const uint32_t cnt = a.n - c < 64u ? a.n - c : 64u;
-    uint64_t w_st = ~0ull, w_len = 0, w_src = 0, w_dst = 0;
-    if (lane < cnt) {
-      w_st = a.start[c + lane];
-      w_len = a.len[c + lane];
-      w_src = a.src[c + lane];
-      w_dst = a.dst_off[c + lane];
-    }
-    bool work = false;
-    for (uint32_t j = 0; j < cnt; ++j) {
-      const uint64_t st = rl64(w_st, j);
-      if (st >= g1) return;
-      const uint64_t len = rl64(w_len, j);
-      if (len == 0) continue;
-      work = true;
-      const uint64_t r0 = g0 > st ? g0 - st : 0;
-      const uint64_t r1 = g1 - st < len ? g1 - st : len;
-      if (r0 < r1)
-        copy_range(a.dst + rl64(w_dst, j) + r0,
-                   reinterpret_cast<const uint8_t*>((uintptr_t)rl64(w_src, j)) + r0, r1 - r0, lane);
-    }
-    // A window of empty jobs (e.g. the encryption-key slot of messages without one: cost 0, all
-    // at one start) may be the head of a long run; jump to its end instead of walking it 64 at a time.
-    uint32_t next = c + cnt;
-    if (!work && next < a.n) {
-      const uint32_t far = __builtin_amdgcn_readfirstlane(find_job(a.start, a.n, rl64(w_st, cnt - 1), lane));
-      next = far > next ? far : next;
-    }
-    c = next;
-  }
+  uint64_t w_src = 0, w_dst = 0;
+  cost_share_walk(
+      a.start, a.len, a.n, wave, nwaves, lane,
+      [&](uint32_t i) {
+        w_src = a.src[i];
+        w_dst = a.dst_off[i];
+      },
+      [&](uint32_t j, uint64_t r0, uint64_t n) {
+        copy_range(a.dst + readlane64(w_dst, j) + r0,
+                   reinterpret_cast<const uint8_t*>((uintptr_t)readlane64(w_src, j)) + r0, n, lane);
+      });
 }
 
 hipError_t launch_put_layout(const PutArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(put_layout_kernel, dim3((uint32_t)((a.m + 255) / 256)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(put_layout_kernel, blocks_for(a.m), 256, s, a);
 }
 
 hipError_t launch_put_seal(const PutArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(put_seal_kernel, dim3((uint32_t)((kPutSlots * a.m + 255) / 256)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(put_seal_kernel, blocks_for(kPutSlots * a.m), 256, s, a);
 }
 
 hipError_t launch_gather_copy(const CopyArgs& a, int grid, hipStream_t s) {
-  if (a.n == 0) return hipSuccess;
-  hipLaunchKernelGGL(gather_copy_kernel, dim3(grid), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(gather_copy_kernel, a.n ? (uint32_t)grid : 0u, 256, s, a);
 }
 
 }  // namespace ambrycrc

@@ -29,6 +29,7 @@
 #include "crc_img.h"
 #include "msg_parse.h"
 #include "recover.h"
+#include "wave_tools.h"
 
 namespace ambrycrc {
 
@@ -93,11 +94,9 @@ __device__ __forceinline__ uint32_t find_node(const uint64_t* __restrict__ pos, 
   return lo < n && pos[lo] == key ? lo : kNoNode;
 }
 
-uint32_t capped_blocks(uint64_t items, int num_cu, uint32_t per_cu) {
-  uint64_t blocks = (items + 255) / 256;
-  const uint64_t cap = (uint64_t)(num_cu > 0 ? num_cu : 1) * per_cu;
-  if (blocks > cap) blocks = cap;
-  return (uint32_t)(blocks ? blocks : 1);
+// The thread-per-message kernels' grid: capped, and one block for an empty chain (they still run).
+uint32_t msg_blocks(const ChainArgs& a, int num_cu, uint32_t per_cu) {
+  return blocks_for(a.max_m ? a.max_m : 1, num_cu, per_cu);
 }
 
 }  // namespace
@@ -415,64 +414,44 @@ __global__ void recover_finish_kernel(ChainArgs a) {
 }
 
 hipError_t launch_chain_scan(const ChainArgs& a, int num_cu, hipStream_t s) {
-  if (a.nblocks == 0) return hipSuccess;
-  uint64_t blocks = a.nblocks;
-  const uint64_t cap = (uint64_t)(num_cu > 0 ? num_cu : 1) * 8;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(chain_scan_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(chain_scan_kernel, blocks_for(a.nblocks, num_cu, 8, 1), 256, s, a);
 }
 
 hipError_t launch_chain_tile_sums(const ChainArgs& a, hipStream_t s) {
-  if (a.ntiles == 0) return hipSuccess;
-  hipLaunchKernelGGL(chain_tile_sums_kernel, dim3((uint32_t)a.ntiles), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(chain_tile_sums_kernel, (uint32_t)a.ntiles, 256, s, a);
 }
 
 hipError_t launch_chain_prefix(const ChainArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(chain_prefix_kernel, dim3(1), dim3(1024), 0, s, a);
-  return hipGetLastError();
+  return launch_items(chain_prefix_kernel, 1, 1024, s, a);
 }
 
 hipError_t launch_chain_compact(const ChainArgs& a, hipStream_t s) {
-  if (a.ntiles == 0) return hipSuccess;
-  hipLaunchKernelGGL(chain_compact_kernel, dim3((uint32_t)a.ntiles), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(chain_compact_kernel, (uint32_t)a.ntiles, 256, s, a);
 }
 
 hipError_t launch_chain_rescan(const ChainArgs& a, int num_cu, hipStream_t s) {
-  if (a.ntiles == 0) return hipSuccess;
-  uint64_t blocks = a.ntiles;
-  const uint64_t cap = (uint64_t)(num_cu > 0 ? num_cu : 1) * 8;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(chain_rescan_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(chain_rescan_kernel, blocks_for(a.ntiles, num_cu, 8, 1), 256, s, a);
 }
 
 hipError_t launch_chain_link(const ChainArgs& a, int num_cu, hipStream_t s) {
-  hipLaunchKernelGGL(chain_link_kernel, dim3(capped_blocks(a.max_m, num_cu, 8)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(chain_link_kernel, msg_blocks(a, num_cu, 8), 256, s, a);
 }
 
 hipError_t launch_chain_round(const ChainArgs& a, uint32_t k, int num_cu, hipStream_t s) {
-  hipLaunchKernelGGL(chain_round_kernel, dim3(capped_blocks(a.max_m, num_cu, 8)), dim3(256), 0, s, a, k);
-  return hipGetLastError();
+  return launch_items(chain_round_kernel, msg_blocks(a, num_cu, 8), 256, s, a, k);
 }
 
 hipError_t launch_chain_emit(const ChainArgs& a, int num_cu, hipStream_t s) {
-  hipLaunchKernelGGL(chain_emit_kernel, dim3(capped_blocks(a.max_m, num_cu, 8)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(chain_emit_kernel, msg_blocks(a, num_cu, 8), 256, s, a);
 }
 
 // As msg_parse_kernel's grid: 2 blocks of 256 a CU, looping past it.
 hipError_t launch_recover_info(const ChainArgs& a, int num_cu, hipStream_t s) {
-  hipLaunchKernelGGL(recover_info_kernel, dim3(capped_blocks(a.max_m, num_cu, 2)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return launch_items(recover_info_kernel, msg_blocks(a, num_cu, 2), 256, s, a);
 }
 
 hipError_t launch_recover_finish(const ChainArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(recover_finish_kernel, dim3(1), dim3(1), 0, s, a);
-  return hipGetLastError();
+  return launch_items(recover_finish_kernel, 1, 1, s, a);
 }
 
 }  // namespace ambrycrc

@@ -17,19 +17,10 @@
 #include "crc_img.h"
 #include "msg_parse.h"
 #include "region_crc.h"
+#include "wave_tools.h"
 
 namespace ambrycrc {
 namespace region {
-
-
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint64_t w = __shfl_xor(v, o);
-    v = w > v ? w : v;
-  }
-  return v;
-}
 
 template <int LVL>
 __device__ __forceinline__ uint32_t wave_fold(uint32_t s, uint32_t c, uint32_t lane) {

@@ -29,6 +29,7 @@
 #include "put_layout.h"
 #include "record_fields.h"
 #include "rekey.h"
+#include "wave_tools.h"
 
 namespace ambrycrc {
 
@@ -184,28 +185,14 @@ __global__ __launch_bounds__(256) void rekey_write_kernel(RekeyArgs a) {
   }
 }
 
-// Both kernels read a message's fields in dependent steps: as msg_parse_kernel, a capped grid keeps
-// a thread's lines in L2 between them.
-static uint32_t rekey_blocks(uint64_t m) {
-  uint64_t blocks = (m + 255) / 256;
-  int dev = 0, cu = 0;
-  if (hipGetDevice(&dev) == hipSuccess &&
-      hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cu > 0 &&
-      blocks > (uint64_t)cu * 4)
-    blocks = (uint64_t)cu * 4;
-  return (uint32_t)blocks;
+// Both kernels read a message's fields in dependent steps: as msg_parse_kernel, a capped grid (4
+// blocks a CU) keeps a thread's lines in L2 between them.
+hipError_t launch_rekey_plan(const RekeyArgs& a, int num_cu, hipStream_t s) {
+  return launch_items(rekey_plan_kernel, blocks_for(a.m, num_cu, 4), 256, s, a);
 }
 
-hipError_t launch_rekey_plan(const RekeyArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(rekey_plan_kernel, dim3(rekey_blocks(a.m)), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_rekey_write(const RekeyArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(rekey_write_kernel, dim3(rekey_blocks(a.m)), dim3(256), 0, s, a);
-  return hipGetLastError();
+hipError_t launch_rekey_write(const RekeyArgs& a, int num_cu, hipStream_t s) {
+  return launch_items(rekey_write_kernel, blocks_for(a.m, num_cu, 4), 256, s, a);
 }
 
 }  // namespace ambrycrc

@@ -25,6 +25,7 @@
 #include "../../include/ambrycrc.h"
 #include "crc32_kernels.h"
 #include "send.h"
+#include "wave_tools.h"
 
 namespace ambrycrc {
 
@@ -155,34 +156,18 @@ __global__ __launch_bounds__(256) void send_finish_kernel(SendArgs a) {
   }
 }
 
-// As the re-key's thread-per-message kernels: a capped grid that loops keeps a thread's lines in L2
-// between its dependent reads.
-static uint32_t send_blocks(uint64_t m) {
-  uint64_t blocks = (m + 255) / 256;
-  int dev = 0, cu = 0;
-  if (hipGetDevice(&dev) == hipSuccess &&
-      hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cu > 0 &&
-      blocks > (uint64_t)cu * 4)
-    blocks = (uint64_t)cu * 4;
-  return (uint32_t)blocks;
+// As the re-key's thread-per-message kernels: a capped grid (4 blocks a CU) that loops keeps a
+// thread's lines in L2 between its dependent reads.
+hipError_t launch_send_plan(const SendArgs& a, int num_cu, hipStream_t s) {
+  return launch_items(send_plan_kernel, blocks_for(a.m, num_cu, 4), 256, s, a);
 }
 
-hipError_t launch_send_plan(const SendArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(send_plan_kernel, dim3(send_blocks(a.m)), dim3(256), 0, s, a);
-  return hipGetLastError();
+hipError_t launch_send_jobs(const SendArgs& a, int num_cu, hipStream_t s) {
+  return launch_items(send_jobs_kernel, blocks_for(a.m, num_cu, 4), 256, s, a);
 }
 
-hipError_t launch_send_jobs(const SendArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(send_jobs_kernel, dim3(send_blocks(a.m)), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_send_finish(const SendArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(send_finish_kernel, dim3(send_blocks(a.m)), dim3(256), 0, s, a);
-  return hipGetLastError();
+hipError_t launch_send_finish(const SendArgs& a, int num_cu, hipStream_t s) {
+  return launch_items(send_finish_kernel, blocks_for(a.m, num_cu, 4), 256, s, a);
 }
 
 }  // namespace ambrycrc

@@ -186,6 +186,50 @@ def test_all_refused_and_all_skipped_write_nothing(messages):
     assert (out == 0xA5).all()
 
 
+@functools.lru_cache(maxsize=None)
+def small_stored_puts():
+    """300 clean stored PUTs with blobs under 1 KiB: headers V1..V3, SerDe V1..V5, blob records V1..V3, every
+    other V2 / V3 one with an encryption key."""
+    out = []
+    for k in range(300):
+        n = (k * 131) % 1024
+        out.append(RK.stored_put(MF.store_key("s%d" % k), MF.blob_properties_bytes(n, serde_version=1 + k % 5),
+                                 b"u" * (k % 7), stream_bytes(400 + k, 0, n).tobytes(), hv=1 + k % 3, bv=1 + k % 3,
+                                 enc_key=b"e" * (1 + k % 40) if k % 2 else None))
+    return out
+
+
+@pytest.mark.parametrize("where", ["start", "middle", "end"])
+@pytest.mark.parametrize("run", [40, 64, 200])
+def test_runs_of_refused_messages(messages, run, where):
+    """A run of consecutive messages the verify refuses (an update message, a wrong blob CRC, a wrong header CRC,
+    by turns; every descriptor usable): rekey_write_kernel leaves each of them four copy jobs of cost 0, so with
+    the jobs slot-major every slot holds `run` empty jobs at one start. gather_copy_kernel reads jobs in windows
+    of 64 from the job its share begins in and jumps from a window of empty jobs to the end of the run: 40 end
+    inside the window after the one that reaches them, 64 can fill a window, 200 leave whole empty windows, so
+    the jump is taken and must land on the first job after the run. At the start of the batch the search for the
+    first share's job must skip the run; at the end the last slot's run starts at the total cost."""
+    from test_gpu_hard_delete import refused_messages
+
+    puts = small_stored_puts()
+    bad = refused_messages(run, "r%d" % run)
+    first = {"start": 0, "middle": 150, "end": len(puts)}[where]
+    msgs = puts[:first] + bad + puts[first:]
+    offs = [int(x) for x in np.cumsum([0] + [len(x) for x in msgs[:-1]])]
+    region = b"".join(msgs)
+    descs, aux = RK.build_descs(offs, [False] * len(msgs), seed=9, skip_frac=0.0, bad_frac=0.0)
+    exp = RK.expected(region, offs, descs, aux)
+    est = exp[0]
+    assert all(est[first:first + run]) and sum(1 for s in est if s) == run
+    assert len(set(est[first:first + run])) == 3
+    got = run_gpu(messages, region, offs, descs, aux, shift=1, oshift=7)
+    assert_outputs(got, exp)
+    cst, couts = RK.run_cpu(messages, region, offs, descs, aux)
+    assert cst == got[0]
+    for b, o, n in zip(couts, got[1], got[2]):
+        assert (b or b"") == got[3][o:o + n].tobytes() if n else not b
+
+
 def test_graph_capture_and_replay(messages):
     """The call only enqueues work, so with a caller workspace it can be captured into a HIP graph and replayed
     on fresh data, with the outputs of the uncaptured call."""

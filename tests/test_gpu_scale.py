@@ -4,7 +4,7 @@ grid of 256-thread blocks and loop over messages past it:
     msg_parse_kernel                   AMBRY_PARSE_BPC = 2 blocks per CU
     region_msg_kernel                  AMBRY_REGION_BPC = AMBRY_REGION_BPC_SMALL = 2
     put_stream_seal_kernel             AMBRY_SEAL_BPC = 2
-    rekey_plan_kernel, rekey_write_kernel   4 (rekey_blocks, rekey_kernels.hip)
+    rekey_plan_kernel, rekey_write_kernel   4 (their launchers, rekey_kernels.hip)
 
 (build_knobs.h; the values are not readable at run time). The batches here hold m = K x T messages with
 m > 2 x 4 x 256 x CUs, about 525,000 on 256 CUs: every thread of a grid capped at 4 blocks per CU takes at least
