@@ -201,6 +201,9 @@ struct DevCtx {
   MsgSlab msg_slab[kSlabs];
   bool xform_slabs_ready = false;
   XformSlab xform_slab[kSlabs];
+  // What the last GPU-leg host call staged (ambrycrc_last_host_slabs): slabs committed, messages sent
+  // down the oversize path; stored under mu as the call ends.
+  uint64_t last_host_slabs = 0, last_host_oversize = 0;
   std::mutex mu;     // guards the slabs (held across a whole host-path call)
   std::mutex ev_mu;  // guards the timing events (taken inside enqueue_batch, which host-path calls reach with mu held)
 };

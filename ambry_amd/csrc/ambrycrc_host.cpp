@@ -371,19 +371,27 @@ enum Staging { kStageBatch, kStageMessages, kStageTransform };
 
 // ------------------------------------------------------------ one GPU-leg call
 // Holds the device's slabs (c->mu) for the whole call with the call's device current and the
-// slabs the leg needs set up; the caller's current device is restored on every way out.
+// slabs the leg needs set up; the caller's current device is restored on every way out. What the
+// call staged -- slabs committed, messages sent down the oversize path -- is stored in the context
+// as the call ends, still under c->mu (ambrycrc_last_host_slabs).
 struct HostCall {
   std::lock_guard<std::mutex> lock;
+  DevCtx* ctx;
   int prev = 0;
   int rc = AMBRYCRC_OK;
-  HostCall(DevCtx* c, int device, Staging need) : lock(c->mu) {
+  uint64_t slabs = 0, oversize = 0;
+  HostCall(DevCtx* c, int device, Staging need) : lock(c->mu), ctx(c) {
     (void)hipGetDevice(&prev);
     rc = hip_err(hipSetDevice(device));
     if (!rc) rc = setup_slabs(c->slab, c->slabs_ready);
     if (!rc && need >= kStageMessages) rc = setup_slabs(c->msg_slab, c->msg_slabs_ready);
     if (!rc && need >= kStageTransform) rc = setup_slabs(c->xform_slab, c->xform_slabs_ready);
   }
-  ~HostCall() { (void)hipSetDevice(prev); }
+  ~HostCall() {
+    ctx->last_host_slabs = slabs;
+    ctx->last_host_oversize = oversize;
+    (void)hipSetDevice(prev);
+  }
 };
 
 // The ring of c's kSlabs staging slabs over one call. A leg fills the slab acquire() gives it,
@@ -399,7 +407,8 @@ struct HostCall {
 template <class Rec>
 class SlabRing {
  public:
-  SlabRing(DevCtx* c, std::function<void(int, Rec&)> consume) : c_(c), consume_(std::move(consume)) {}
+  SlabRing(DevCtx* c, HostCall& call, std::function<void(int, Rec&)> consume)
+      : c_(c), call_(call), consume_(std::move(consume)) {}
   bool ok() const { return rc_ == AMBRYCRC_OK; }
   void fail(int rc) {
     if (ok()) rc_ = rc;
@@ -423,6 +432,7 @@ class SlabRing {
     }
     busy_[slot()] = true;
     ++k_;
+    ++call_.slabs;
     return true;
   }
   // Waits for and consumes everything in flight, oldest first; the call's status.
@@ -440,6 +450,7 @@ class SlabRing {
     return AMBRYCRC_OK;
   }
   DevCtx* c_;
+  HostCall& call_;
   std::function<void(int, Rec&)> consume_;
   Rec rec_[kSlabs];
   bool busy_[kSlabs] = {};
@@ -485,7 +496,7 @@ int batch_host_gpu(DevCtx* c, const void* const* ptrs, const uint64_t* lens, con
   };
   std::vector<uint32_t> acc(n, 0u);
   for (size_t i = 0; i < n; ++i) acc[i] = crc_in ? crc_in[i] : 0u;
-  SlabRing<std::vector<Piece>> ring(c, [&](int w, std::vector<Piece>& pieces) {
+  SlabRing<std::vector<Piece>> ring(c, call, [&](int w, std::vector<Piece>& pieces) {
     const uint32_t* h_out = c->slab[w].h_out;
     for (size_t j = 0; j < pieces.size(); ++j)
       acc[pieces[j].chunk] = ambrycrc_combine(acc[pieces[j].chunk], h_out[j], pieces[j].len);
@@ -646,7 +657,7 @@ int verify_messages_host_gpu(DevCtx* c, const uint8_t* region, uint64_t region_l
     uint64_t lo = 0;
     std::vector<size_t> msgs;
   };
-  SlabRing<Span> ring(c, [&](int w, Span& sp) {
+  SlabRing<Span> ring(c, call, [&](int w, Span& sp) {
     const MsgSlab& ms = c->msg_slab[w];
     for (size_t q = 0; q < sp.msgs.size(); ++q) {
       status[sp.msgs[q]] = ms.h_status[q];
@@ -660,6 +671,7 @@ int verify_messages_host_gpu(DevCtx* c, const uint8_t* region, uint64_t region_l
     if (ext[first] > kSlabBytes) {  // (its results do not wait for the slabs in flight: they go by index)
       uint32_t st = 0;
       uint64_t en = 0;
+      ++call.oversize;
       ring.fail(verify_oversize(c, region + lo, ext[first], &st, &en));
       status[first] = st;
       if (msg_end) msg_end[first] = en ? lo + en : 0;
@@ -737,7 +749,7 @@ int transform_messages_host_gpu(DevCtx* c, const uint8_t* region, uint64_t regio
     size_t i0 = 0, n = 0;
   };
   std::vector<CopyJob> jobs;
-  SlabRing<Run> ring(c, [&](int w, Run& r) {
+  SlabRing<Run> ring(c, call, [&](int w, Run& r) {
     const MsgSlab& ms = c->msg_slab[w];
     const XformSlab& x = c->xform_slab[w];
     jobs.clear();
@@ -757,6 +769,7 @@ int transform_messages_host_gpu(DevCtx* c, const uint8_t* region, uint64_t regio
       uint32_t st = 0;
       uint64_t len = 0;
       std::vector<uint8_t> bytes;
+      ++call.oversize;
       int rc = ring.drain_all();  // the output is packed in message order
       if (!rc)
         rc = transform_oversize(region + std::min(msg_off[i], region_len), ext[i], life_version ? life_version + i : nullptr,
@@ -1134,6 +1147,20 @@ int ambrycrc_host_msg_rates(int device, int op, double* cpu_gibps, double* gpu_g
 int ambrycrc_last_host_path(int device) {
   DevCtx* c = ctx_for(device);
   return c ? c->last_host_path.load() : AMBRYCRC_ENOINIT;
+}
+
+int ambrycrc_last_host_slabs(int device, uint64_t info[6]) {
+  DevCtx* c = ctx_for(device);
+  if (!c) return AMBRYCRC_ENOINIT;
+  if (!info) return AMBRYCRC_EINVAL;
+  info[0] = kSlabBytes;
+  info[1] = kSlabChunks;
+  info[2] = kSlabMsgs;
+  info[3] = kXformOutBytes;
+  std::lock_guard<std::mutex> g(c->mu);
+  info[4] = c->last_host_slabs;
+  info[5] = c->last_host_oversize;
+  return AMBRYCRC_OK;
 }
 
 }  // extern "C"

@@ -241,6 +241,16 @@ def last_host_path(device: int = 0) -> int:
     return lib().ambrycrc_last_host_path(device)
 
 
+def last_host_slabs(device: int = 0) -> dict:
+    """The host path's staging geometry and what the device's last GPU-leg host call staged
+    (ambrycrc_last_host_slabs): slab_bytes, slab_chunks, slab_msgs, xform_out_bytes, and the call's
+    slabs (committed) and oversize (messages through the oversize path) counts."""
+    info = (ctypes.c_uint64 * 6)()
+    check(lib().ambrycrc_last_host_slabs(device, info), "ambrycrc_last_host_slabs")
+    return dict(zip(("slab_bytes", "slab_chunks", "slab_msgs", "xform_out_bytes", "slabs", "oversize"),
+                    [int(x) for x in info]))
+
+
 def set_grid(device: int, workgroups: int) -> None:
     check(lib().ambrycrc_set_grid(device, workgroups), "ambrycrc_set_grid")
 

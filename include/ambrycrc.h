@@ -710,6 +710,12 @@ int ambrycrc_set_host_cpu_threads(int device, int threads);
 int ambrycrc_host_calibrate(int device, double* cpu_gibps);
 /* The leg the device's last host call took: 0 CPU, 1 GPU, -1 none yet. */
 int ambrycrc_last_host_path(int device);
+/* The staging geometry of the host path's GPU legs and what the device's last GPU-leg *_host call
+ * staged: info[0..3] = bytes per staging slab, chunk pieces per slab, messages per slab, bytes of a
+ * slab's transform output buffer; info[4] = slabs that call committed; info[5] = messages it sent
+ * down the oversize path (a message larger than a slab, in device buffers of its own). Both counts
+ * are 0 before any such call. AMBRYCRC_ENOINIT without a context, AMBRYCRC_EINVAL for a NULL info. */
+int ambrycrc_last_host_slabs(int device, uint64_t info[6]);
 /* The rates auto compares for the host message entries (op 0: ambrycrc_verify_messages_host, 1:
  * ambrycrc_transform_messages_host), GiB/s of region bytes: each leg's rate as its calls of >= 64 MiB
  * measured it (an EWMA; the CPU leg starts at a share of the CRC rate, the GPU leg at round 5's
