@@ -27,9 +27,9 @@
 #ifndef AMBRY_REGION_AUX  // region pass 2's LDS helpers (region_crc.h Aux): 1 = LDS byte masks + H0, 2 = x^(8*256)
 #define AMBRY_REGION_AUX 7  // byte tables for the Horner steps, 4 = two-multiply un-shift
 #endif
-#ifndef AMBRY_STREAM_PIPE  // serialize copy mode's streamed form: message i+1's loads in flight while i is hashed
-#define AMBRY_STREAM_PIPE 1
-#endif
+// (Serialize copy mode's streamed form keeps message i+1's loads in flight while i is hashed; the
+// form without that, round 6's AMBRY_STREAM_PIPE 0, lives in
+// tools/probes/patches/put_stream_unpipelined.patch: `git apply` it to a scratch tree to rebuild it.)
 #ifndef AMBRY_SEAL_BPC  // serialize copy mode's streamed form: put_stream_seal_kernel blocks per CU
 #define AMBRY_SEAL_BPC 2
 #endif
@@ -55,7 +55,8 @@
 #define AMBRY_FUSED_ENDS 1  // the wait for its run sums: 0 = never, 1 = the transform's copy form, 2 = also the verify
 #endif
 
-// ---- batch CRC kernels (crc32_kernels.hip, crc32_kernels.h, ambrycrc_ctx.h)
+// ---- batch CRC kernels (crc32_kernels.hip, crc32_kernels.h, ambrycrc_ctx.h) and region pass 1
+// (AMBRY_RUNS_*: region_kernels.hip)
 #ifndef AMBRY_GRP_PRIO  // s_setprio 3 around the streamed group path's loads
 #define AMBRY_GRP_PRIO 0
 #endif
@@ -105,7 +106,7 @@
 // X(name, default) for every knob above: ambrycrc_version() reports those that differ.
 #define AMBRY_KNOB_LIST(X)                                                                                  \
   X(AMBRY_PROPS_WIN, 96) X(AMBRY_PARSE_BPC, 2) X(AMBRY_REGION_WPE, 2) X(AMBRY_REGION_BPC, 2)                  \
-  X(AMBRY_REGION_BPC_SMALL, 2) X(AMBRY_REGION_AUX, 7) X(AMBRY_SEAL_BPC, 2) X(AMBRY_STREAM_PIPE, 1) X(AMBRY_HOST_VERIFY_CPU_PCT, 50) X(AMBRY_HOST_XFORM_CPU_PCT, 25)                                                                          \
+  X(AMBRY_REGION_BPC_SMALL, 2) X(AMBRY_REGION_AUX, 7) X(AMBRY_SEAL_BPC, 2) X(AMBRY_HOST_VERIFY_CPU_PCT, 50) X(AMBRY_HOST_XFORM_CPU_PCT, 25)                                                                          \
   X(AMBRY_FUSED_PROC, 0)                                                                                      \
   X(AMBRY_FUSED_WAVES_VERIFY, 12)                                                                               \
   X(AMBRY_FUSED_WAVES_COPY, 8) X(AMBRY_FUSED_NT, 1) X(AMBRY_FUSED_ENDS, 1)                                                                 \

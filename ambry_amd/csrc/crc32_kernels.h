@@ -1,5 +1,6 @@
 // crc32_kernels.h -- launch interface between the C ABI (ambrycrc.cpp) and the
-// gfx950 kernels (crc32_kernels.hip). Internal to libambrycrc.
+// gfx950 kernels (the batch engine crc32_kernels.hip and the other *_kernels.hip files, each named
+// at its argument structs below). Internal to libambrycrc.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -111,7 +112,7 @@ constexpr bool variant_groups(int v) { return v == kVariantDefault || v == kVari
 constexpr int kDiagNoFold = 100;  // diagnostic timing build, selectable via ambrycrc_set_variant only
 
 // Region mode of the message verify: the log region is swept once as contiguous
-// memory, each 64-B run's raw CRC (zero register, no xor-out) stored (crc32_kernels.hip
+// memory, each 64-B run's raw CRC (zero register, no xor-out) stored (region_kernels.hip
 // region_runs_kernel), then one thread per message parses it and assembles its record CRCs from
 // the runs they cover (message_kernels.hip region_msg_kernel, region_crc.h). Runs are [base + 64k, base + 64k + 64) with
 // base = the region's start rounded down to 64 B; only 16-B pieces holding region bytes are read.

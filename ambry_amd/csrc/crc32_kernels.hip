@@ -1,4 +1,8 @@
-// crc32_kernels.hip -- gfx950 (CDNA4) kernels for Ambry's blob CRC-32 path.
+// crc32_kernels.hip -- the batch CRC engine: the gfx950 (CDNA4) kernels for Ambry's blob CRC-32
+// path and their launchers (launch_plan, launch_sweep, launch_sweep_copy, launch_verify,
+// launch_fill). The wave primitives they are built from are in crc_wave.h; region mode, the PUT
+// streamer and the bandwidth probes have kernel files of their own (region_kernels.hip,
+// put_kernels.hip, bw_probe_kernels.hip).
 //
 // Replaces, for device-resident batches of chunks, the byte loop of
 // ambry-utils/.../utils/Crc32.java:55-143 (and java.util.zip.CRC32.update, the
@@ -30,137 +34,10 @@
 #include "crc32_gf2.h"
 #include "crc32_layout.h"
 #include "crc32_kernels.h"
-#include "crc_img.h"
-#include "put_layout.h"
-#include "region_proc.h"
+#include "crc_wave.h"
 #include "wave_tools.h"
 
-// A/B knob: s_setprio 3 around the streamed group path's loads, as the wave-mode body has it.
-
 namespace ambrycrc {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__shared__ __attribute__((aligned(16))) uint32_t g_lds[kLdsBytes / 4];
-
-// Stage the table image into LDS with LDS-DMA (global_load_lds_dwordx4: 1 KiB per wave
-// instruction, no VGPR round trip), all of a wave's ~10 loads in flight together, then one
-// wait and a barrier. A load -> ds_write loop serialises on vmcnt(0) per iteration: ~10
-// memory round trips, which was most of a single-chunk call's sweep-kernel time.
-__device__ __forceinline__ void fill_lds(const uint32_t* __restrict__ img) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  constexpr uint32_t kChunks = (kLdsBytes + 1023) / 1024;
-  for (uint32_t c = wave; c < kChunks; c += nw) {
-    const uint32_t byte = c * 1024 + lane * 16;
-    if (byte < kLdsBytes)
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(reinterpret_cast<const uint8_t*>(img) + byte),
-          (__attribute__((address_space(3))) void*)(reinterpret_cast<uint8_t*>(g_lds) + c * 1024), 16, 0, 0);
-  }
-  __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0) expcnt(0) lgkmcnt(0): the DMA writes have landed
-  __syncthreads();
-}
-
-// Region mode's pass 1 (region_runs_kernel) stages only the slice tables, plus a 1 KiB buffer per
-// wave for its run sums: its own LDS array, so that kernel is not sized by the full image.
-constexpr uint32_t kRunsBufBytes = 1024;
-__shared__ __attribute__((aligned(16))) uint32_t g_lds_runs[(kSliceBytes + 16 * kRunsBufBytes) / 4];
-
-// LDS-DMA of the slice tables (image bytes [0, 128 KiB)) into g_lds_runs, as fill_lds. The issue
-// half alone is for a kernel that stages more before its one wait (region_fused_kernel).
-__device__ __forceinline__ void issue_lds_slices(const uint32_t* __restrict__ img) {
-  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (uint32_t c = wv; c < kSliceBytes / 1024; c += nw)
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)(reinterpret_cast<const uint8_t*>(img) + c * 1024 + lane * 16),
-        (__attribute__((address_space(3))) void*)(reinterpret_cast<uint8_t*>(g_lds_runs) + c * 1024), 16, 0, 0);
-}
-
-__device__ __forceinline__ void fill_lds_slices(const uint32_t* __restrict__ img) {
-  issue_lds_slices(img);
-  __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();
-}
-
-// W = 0: the full image (g_lds); W = 1: the slice tables of region_runs_kernel (g_lds_runs).
-template <int W = 0>
-__device__ __forceinline__ uint32_t lds_rd(uint32_t byte_addr) {
-  const char* base = W == 0 ? reinterpret_cast<const char*>(g_lds) : reinterpret_cast<const char*>(g_lds_runs);
-  return *reinterpret_cast<const uint32_t*>(base + byte_addr);
-}
-
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-}
-
-// Cross-lane moves without LDS: DPP row shifts / broadcasts (lanes with no source read 0).
-template <int CTRL, int ROWS>
-__device__ __forceinline__ uint32_t dpp(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xf, false);
-}
-
-// Value of lane (l - 2^lvl) delivered to every lane l with bit lvl set (the tree's left partner):
-// row_shr:1/2/4/8 inside 16-lane rows, then row_bcast:15 (rows 1,3) and row_bcast:31 (rows 2,3).
-template <int LVL>
-__device__ __forceinline__ uint32_t tree_partner(uint32_t v) {
-  if constexpr (LVL < 4) return dpp<0x110 + (1 << LVL), 0xf>(v);
-  else if constexpr (LVL == 4) return dpp<0x142, 0xa>(v);
-  else return dpp<0x143, 0xc>(v);
-}
-
-// Per-lane address constants for slice table j: region bit, (j&1)*128, lane column.
-struct LaneConst {
-  uint32_t L0, L1, L2, L3;
-};
-
-__device__ __forceinline__ LaneConst make_lane_const(uint32_t lane) {
-  const uint32_t col = (lane & 31u) << 2;
-  LaneConst k;
-  k.L0 = (0u << 16) | (0u << 7) | col;
-  k.L1 = (0u << 16) | (1u << 7) | col;
-  k.L2 = (1u << 16) | (0u << 7) | col;
-  k.L3 = (1u << 16) | (1u << 7) | col;
-  return k;
-}
-
-// One slice-by-4 step on x = state ^ word: T3[x.b0]^T2[x.b1]^T1[x.b2]^T0[x.b3] ^ xin.
-// perm(L, x, sel): result byte0 = L.b0 (lane column), byte1 = x.b_k, byte2 = L.b2 (region), byte3 = 0.
-template <int W = 0>
-__device__ __forceinline__ uint32_t slice4(uint32_t x, const LaneConst& k, uint32_t xin) {
-  const uint32_t a0 = __builtin_amdgcn_perm(k.L3, x, 0x0C060004u);
-  const uint32_t a1 = __builtin_amdgcn_perm(k.L2, x, 0x0C060104u);
-  const uint32_t a2 = __builtin_amdgcn_perm(k.L1, x, 0x0C060204u);
-  const uint32_t a3 = __builtin_amdgcn_perm(k.L0, x, 0x0C060304u);
-  const uint32_t t = xor3(lds_rd<W>(a0), lds_rd<W>(a1), lds_rd<W>(a2));
-  return xor3(t, lds_rd<W>(a3), xin);
-}
-
-// Raw CRC (zero register, no xor-out) of one 16-B piece, xor xin.
-__device__ __forceinline__ uint32_t rpiece(u32x4 w, const LaneConst& k, uint32_t xin) {
-  uint32_t s = slice4(w.x, k, w.y);
-  s = slice4(s, k, w.z);
-  s = slice4(s, k, w.w);
-  return slice4(s, k, xin);
-}
-
-// v * C mod P where C's nibble tables sit at kNibBase + set_off (conflict-free, 8 lookups).
-__device__ __forceinline__ uint32_t nib_mul(uint32_t v, uint32_t set_off) {
-  uint32_t t[8];
-#pragma unroll
-  for (int n = 0; n < 8; ++n)
-    t[n] = lds_rd(kNibBase + set_off + 64u * n + (__builtin_amdgcn_ubfe(v, 4 * n, 4) << 2));
-  return xor3(xor3(t[0], t[1], t[2]), xor3(t[3], t[4], t[5]), t[6] ^ t[7]);
-}
-
-// v * x^(8n) mod P for a wave-uniform n (register advanced over n zero bytes).
-__device__ __forceinline__ uint32_t shift_bytes(uint32_t v, uint64_t n, const uint32_t* __restrict__ xpow2) {
-  while (n) {
-    const uint32_t k = (uint32_t)__builtin_ctzll(n);
-    n &= n - 1;
-    v = (k < kPowTables) ? nib_mul(v, kPowOff + kNibSetBytes * k) : gf2_mul(v, xpow2[k]);
-  }
-  return v;
-}
 
 template <int DIAG>
 __device__ __forceinline__ uint32_t fold(uint32_t s) {
@@ -183,69 +60,6 @@ __device__ __forceinline__ uint32_t rpiece_pair_d(u32x4 w0, u32x4 w1, const Lane
   x1 = slice4(x1, k, w1.w);
   s = slice4(x0, k, fold<DIAG>(s));
   return slice4(x1, k, fold<DIAG>(s));
-}
-
-template <bool NT>
-__device__ __forceinline__ u32x4 ld16(const u32x4* p) {
-  if constexpr (NT) {
-    return __builtin_nontemporal_load(p);
-  } else {
-    return *p;
-  }
-}
-
-// ---- copy-through (SweepArgs::copy_dst): every byte read for a chunk is also stored to the
-// chunk's destination, dbase + (its source offset), so a serialization moves each field once.
-// 16-B stores at any destination alignment (gfx9 global memory runs in unaligned mode; the
-// memcpy becomes one global_store_dwordx4); a piece that starts before the chunk stores only
-// its bytes from `lo` on.
-// The destination pointers are built from integers (SweepArgs::copy_off), which leaves them in
-// the generic address space: a store through one is a flat_store, which counts on lgkmcnt as well
-// as vmcnt, so every LDS wait of the CRC chain would also wait for the outstanding stores. The
-// casts keep them global_store.
-typedef __attribute__((address_space(1))) u32x4 gu32x4;
-typedef __attribute__((address_space(1))) uint8_t gu8;
-__device__ __forceinline__ void st8g(uint8_t* d, uint32_t v) { *(gu8*)d = (uint8_t)v; }
-__device__ __forceinline__ void st16u(uint8_t* d, const u32x4& v) { *(gu32x4*)d = v; }
-// Wave-mode bodies (large chunks) stream their stores nontemporal: 3-5 % faster there, 18 %
-// slower in the group phase's short records (r02x A/B), which keep the plain store.
-__device__ __forceinline__ void st16u_nt(uint8_t* d, const u32x4& v) { __builtin_nontemporal_store(v, (gu32x4*)d); }
-
-__device__ __forceinline__ void copy_piece(uint8_t* dbase, int64_t p, const u32x4& v, int64_t lo) {
-  if (!dbase || p + 16 <= lo) return;  // null: a chunk read but not copied (kCopySkip)
-  if (p >= lo) {
-    st16u(dbase + p, v);
-    return;
-  }
-#pragma unroll
-  for (int b = 0; b < 16; ++b)
-    if (p + b >= lo) st8g(dbase + p + b, v[b >> 2] >> (8 * (b & 3)));
-}
-
-template <int LVL>
-__device__ __forceinline__ uint32_t tree_level(uint32_t s, uint32_t lane) {
-  const uint32_t sh = nib_mul(tree_partner<LVL>(s), kTreeOff + kNibSetBytes * LVL);
-  return (lane & (1u << LVL)) ? (s ^ sh) : s;
-}
-
-// Raw CRC (zero register) of the t < 16 bytes at p, lane-parallel: lane j holds byte j, whose
-// contribution is T0[b] advanced over the t-1-j bytes after it = T_{k&3}[b] * x^(32*(k>>2)),
-// k = t-1-j; then an XOR over the 16 lanes of row 0. Result valid in every lane of row 0.
-__device__ __forceinline__ uint32_t tail_crc(const uint8_t* __restrict__ p, uint32_t t, uint32_t lane) {
-  uint32_t v = 0;
-  if (lane < t) {
-    const uint32_t b = p[lane];
-    const uint32_t k = t - 1 - lane;
-    const uint32_t j = k & 3;
-    v = lds_rd(((j >> 1) << 16) | (b << 8) | ((j & 1) << 7) | ((lane & 31) << 2));
-    if (k & 4) v = nib_mul(v, kPowOff + kNibSetBytes * 2);  // x^(8*4)
-    if (k & 8) v = nib_mul(v, kPowOff + kNibSetBytes * 3);  // x^(8*8)
-  }
-  v ^= dpp<0x128, 0xf>(v);  // row_ror:8
-  v ^= dpp<0x124, 0xf>(v);  // row_ror:4
-  v ^= dpp<0x122, 0xf>(v);  // row_ror:2
-  v ^= dpp<0x121, 0xf>(v);  // row_ror:1
-  return v;
 }
 
 // Block 0 of a body whose virtual start v0 = be - nb*1024 may precede bs: lane l's 16 B at
@@ -331,71 +145,12 @@ __device__ __forceinline__ uint32_t body_crc(const uint8_t* __restrict__ base, u
   return s;
 }
 
-// Raw CRC of a lane's run of R consecutive 16-B pieces (R slice-by-4 chains of 4 steps, back
-// to back), xor xin into the last step.
-template <int R, int W = 0>
-__device__ __forceinline__ uint32_t run_crc(const u32x4 (&w)[R], const LaneConst& k, uint32_t xin) {
-  uint32_t x = w[0].x;
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    x = slice4<W>(x, k, w[r].y);
-    x = slice4<W>(x, k, w[r].z);
-    x = slice4<W>(x, k, w[r].w);
-    x = slice4<W>(x, k, r + 1 < R ? w[r + 1].x : xin);
-  }
-  return x;
-}
-
 // ---- 64-B lane runs from coalesced loads (variant 12 and up) ----
 // Per 4 KiB super-block each lane l = 4m+j issues 4 coalesced 1 KiB loads (block i, piece l),
 // then a 4x4 transpose of 16-B elements inside its quad (two DPP quad_perm butterfly stages)
 // leaves lane (m, j) holding the 64-B run [64m, 64m+64) of block j: the state hops once per
 // 64 B (x^(8*4096) = POW[12]) instead of once per 16 B. Tree: lane bits 2..5 merge the runs of
 // one block (shifts 64..512 B = POW[6..9]), bits 0..1 merge the blocks (1024, 2048 B).
-template <int CTRL>
-__device__ __forceinline__ uint32_t dppq(uint32_t v) {  // quad_perm: every lane has a source
-  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xf, 0xf, true);
-}
-
-// A 4x4 transpose of 16-B elements inside each lane quad, with the lane selects fused into the DPP moves: v_cndmask_b32_dpp
-// computes vcc ? src1 : dpp(src0), so each stage is 4 VALU ops per dword instead of 4 DPP
-// moves + 4 v_cndmask_b32_e64 (the compiler cannot fuse them: its selects take the lane
-// mask from an SGPR pair, the VOP3 form, which has no DPP encoding on gfx9). 8 VALU per
-// dword per transpose instead of 16. s_nop 1 on entry and exit covers the gfx9 hazard of
-// a DPP read within 2 wait states of the VALU write of its source.
-__device__ __forceinline__ void quad_transpose_asm(u32x4 (&x)[4]) {
-  const uint64_t m1 = 0xAAAAAAAAAAAAAAAAull, n1 = 0x5555555555555555ull;  // lane & 1 set / clear
-  const uint64_t m2 = 0xCCCCCCCCCCCCCCCCull, n2 = 0x3333333333333333ull;  // lane & 2 set / clear
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    uint32_t a0, a1, a2, a3, y0, y1, y2, y3;
-    asm volatile(
-        "s_nop 1\n\t"
-        "s_mov_b64 vcc, %[n1]\n\t"
-        "v_cndmask_b32_dpp %[a0], %[x1], %[x0], vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_dpp %[a2], %[x3], %[x2], vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_mov_b64 vcc, %[m1]\n\t"
-        "v_cndmask_b32_dpp %[a1], %[x0], %[x1], vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_dpp %[a3], %[x2], %[x3], vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_mov_b64 vcc, %[n2]\n\t"
-        "v_cndmask_b32_dpp %[y0], %[a2], %[a0], vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_dpp %[y1], %[a3], %[a1], vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "s_mov_b64 vcc, %[m2]\n\t"
-        "v_cndmask_b32_dpp %[y2], %[a0], %[a2], vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_dpp %[y3], %[a1], %[a3], vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1"
-        : [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3), [y0] "=&v"(y0), [y1] "=&v"(y1),
-          [y2] "=&v"(y2), [y3] "=&v"(y3)
-        : [x0] "v"(x[0][d]), [x1] "v"(x[1][d]), [x2] "v"(x[2][d]), [x3] "v"(x[3][d]), [m1] "s"(m1), [n1] "s"(n1),
-          [m2] "s"(m2), [n2] "s"(n2)
-        : "vcc");
-    x[0][d] = y0;
-    x[1][d] = y1;
-    x[2][d] = y2;
-    x[3][d] = y3;
-  }
-}
-
 template <int BIT, int POWK>
 __device__ __forceinline__ uint32_t tree_level_t4(uint32_t s, uint32_t lane) {
   uint32_t o;
@@ -1518,732 +1273,6 @@ hipError_t launch_sweep_copy(const SweepArgs& a, int grid, int num_cu, int varia
   return hipGetLastError();
 }
 
-// ---- region mode, pass 1 (RegionArgs): the raw CRC of every 64-B run of a log region ----
-// The wave body of C3 without its fold and tree: each wave streams a contiguous share of 4 KiB
-// super-blocks (four coalesced 1 KiB loads per lane, nontemporal, s_setprio 3 while issuing
-// them, the next super-block in flight), the quad transpose leaves lane 4m + j the run
-// [64m, 64m + 64) of block j, one 16-step slice-by-4 chain from a zero register gives its raw
-// CRC, stored at run index 16j + m of the super-block. Loads are unconditional: a piece outside
-// the region reads the nearest piece that holds region bytes, zeroed after (the run sums of
-// runs that straddle the region's ends are never used; region_msg_kernel (region_crc.h) recomputes those
-// runs from the bytes). Runs have no loop-carried state, so consecutive super-blocks' chains
-// are independent.
-template <bool NT = true>
-__device__ __forceinline__ void region_sb_load(const RegionArgs& a, uint64_t s, uint32_t lane, u32x4 (&x)[4]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const uint64_t p = s * kSuperBlock + (uint64_t)kBlockBytes * i + 16u * lane;
-    const uint64_t q = p < a.lo16 ? a.lo16 : (p > a.hi16 ? a.hi16 : p);
-    x[i] = ld16<NT>(reinterpret_cast<const u32x4*>(a.base + q));
-  }
-}
-
-__device__ __forceinline__ void region_sb_zero(const RegionArgs& a, uint64_t s, uint32_t lane, u32x4 (&x)[4]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const uint64_t p = s * kSuperBlock + (uint64_t)kBlockBytes * i + 16u * lane;
-    if (p < a.lo16 || p > a.hi16) x[i] = u32x4{0u, 0u, 0u, 0u};
-  }
-}
-
-// A/B knobs: AMBRY_RUNS_PROBE 1 = no run sums into LDS, 5 = no global stores,
-// 6 = every wave's stores to one 1 KiB line set (timing only, wrong sums); AMBRY_RUNS_STORE_NT 0 =
-// plain stores.
-__global__ __launch_bounds__(1024) void region_runs_kernel(RegionArgs a) {
-  if (a.lng.ctr && blockIdx.x == 0 && threadIdx.x == 0) {  // pass 2's long-record list starts empty
-    *a.lng.ctr = 0;
-    *a.lng.claim = 0;
-  }
-  const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
-  // Shares wave-major over workgroups, as the sweep kernel's (CU-major shares measured the same).
-  const uint32_t wave = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) * gridDim.x + blockIdx.x);
-  fill_lds_slices(a.img);
-  const uint32_t lane = threadIdx.x & 63u;
-  const LaneConst k = make_lane_const(lane);
-  // Groups of four super-blocks: contiguous shares (wave w: [s0, s1) in steps of 4), or with
-  // AMBRY_RUNS_GIL interleaved over the waves (wave w: groups w, w + nwaves, ...), which keeps all
-  // waves' concurrent reads inside a 64 MiB window and their stores inside 4 MiB.
-#if AMBRY_RUNS_GIL
-  const uint64_t first = 4 * (uint64_t)wave, step = 4 * nwaves, end = a.nsb;
-#else
-  const uint64_t first = a.nsb * wave / nwaves, step = 4, end = a.nsb * (wave + 1) / nwaves;
-#endif
-  if (first >= end) return;
-  // Four super-block buffers: while one is hashed the next three are in flight. Each buffer is
-  // hashed in place and only then reloaded (no register copies of loads still in flight), and every
-  // load and store is issued on every path (indices past the end re-read the last super-block;
-  // lanes with nothing to store write the workspace's spill line), so each wait is for the oldest
-  // buffer only. A group's four super-blocks' sums gather in the wave's LDS buffer (word 64u + run
-  // index) and go out as one 16-B store per lane: 1 KiB contiguous per wave, 8 whole 128-B lines.
-  uint32_t* buf = g_lds_runs + kSliceBytes / 4 + (threadIdx.x >> 6) * (kRunsBufBytes / 4);
-  const uint32_t slot = 16u * (lane & 3u) + (lane >> 2);
-  const uint64_t slast = end - 1;
-  auto at = [&](uint64_t s) { return s < end ? s : slast; };
-  auto hash = [&](uint64_t s, uint32_t u, u32x4 (&cur)[4]) {
-    region_sb_zero(a, s, lane, cur);
-    quad_transpose_asm(cur);
-    const uint32_t r = run_crc<4, 1>(cur, k, 0u);
-    if (AMBRY_RUNS_PROBE == 0 || r == 0x9E3779B9u) buf[64u * u + slot] = r;
-  };
-  u32x4 b0[4], b1[4], b2[4], b3[4];
-  region_sb_load<AMBRY_RUNS_NT != 0>(a, first, lane, b0);
-  region_sb_load<AMBRY_RUNS_NT != 0>(a, at(first + 1), lane, b1);
-  region_sb_load<AMBRY_RUNS_NT != 0>(a, at(first + 2), lane, b2);
-  region_sb_load<AMBRY_RUNS_NT != 0>(a, at(first + 3), lane, b3);
-  u32x4* spill = reinterpret_cast<u32x4*>(a.rk + kRunPad + a.nsb * 64) + lane;
-  for (uint64_t g = first; g < end; g += step) {
-    const uint64_t nx = g + step;
-    hash(g, 0, b0);
-    __builtin_amdgcn_s_setprio(3);
-    region_sb_load<AMBRY_RUNS_NT != 0>(a, at(nx), lane, b0);
-    __builtin_amdgcn_s_setprio(0);
-    if (g + 1 < end) hash(g + 1, 1, b1);
-    __builtin_amdgcn_s_setprio(3);
-    region_sb_load<AMBRY_RUNS_NT != 0>(a, at(nx + 1), lane, b1);
-    __builtin_amdgcn_s_setprio(0);
-    if (g + 2 < end) hash(g + 2, 2, b2);
-    __builtin_amdgcn_s_setprio(3);
-    region_sb_load<AMBRY_RUNS_NT != 0>(a, at(nx + 2), lane, b2);
-    __builtin_amdgcn_s_setprio(0);
-    if (g + 3 < end) hash(g + 3, 3, b3);
-    __builtin_amdgcn_s_setprio(3);
-    region_sb_load<AMBRY_RUNS_NT != 0>(a, at(nx + 3), lane, b3);
-    __builtin_amdgcn_s_setprio(0);
-    const u32x4 v = *reinterpret_cast<const u32x4*>(buf + 4u * lane);
-    u32x4* dst = 4u * lane < 64u * (end - g) ? reinterpret_cast<u32x4*>(a.rk + kRunPad + g * 64) + lane : spill;
-    if constexpr (AMBRY_RUNS_PROBE == 6) dst = reinterpret_cast<u32x4*>(a.rk + kRunPad) + lane;
-    if constexpr (AMBRY_RUNS_PROBE == 5) {
-      if (v.x == 0x9E3779B9u) *dst = v;
-    } else if constexpr (AMBRY_RUNS_STORE_NT) {
-      __builtin_nontemporal_store(v, dst);
-    } else {
-      *dst = v;
-    }
-  }
-}
-
-hipError_t launch_region_runs(const RegionArgs& a, int grid, hipStream_t s) {
-  return launch_items(region_runs_kernel, a.nsb ? (uint32_t)grid : 0u, 1024, s, a);
-}
-
-// ---- copy-mode serialization of small messages (put_stream_kernel; StreamPutArgs, crc32_kernels.h) ----
-// The uniform layout of one message (PutMessageFormatInputStream.java:76-124 through put_layout.h):
-// five data segments copied from their sources and six gaps between them -- the header, the record
-// prefixes and trailers -- whose bytes are computed (every CRC field zero here: put_stream_seal_kernel
-// writes them). Segments and gaps alternate: gap g = [hi[g-1], lo[g]) (hi[-1] = 0, lo[5] = len), an
-// absent encryption key an empty segment at the key's end.
-struct StreamMsg {
-  int32_t len;                    // message bytes (<= kStreamPutMax)
-  int32_t lo[5], hi[5];           // data segment k at [lo, hi) of the message (key, enc key, props, um, blob)
-  const uint8_t* src[5];          // its source
-};
-
-__device__ __forceinline__ bool stream_msg(const ambrycrc_put_desc& d, const uint8_t* fields, const uint8_t* blobs,
-                                           StreamMsg& M) {
-  PutLayout L;
-  if (!put_layout(d, L) || L.length > kStreamPutMax) return false;
-  M.len = (int32_t)L.length;
-  uint64_t fo[5];
-  put_field_offsets(d, L, fo);
-  const uint64_t ln[5] = {d.key_len, L.enc_rec ? (uint64_t)d.enckey_len : 0, d.props_len, d.usermeta_len, d.blob_len};
-  const uint64_t so[5] = {d.key_src, d.enckey_src, d.props_src, d.usermeta_src, d.blob_src};
-  if (!L.enc_rec) fo[1] = fo[0] + ln[0];  // the empty segment at the key's end
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    M.lo[k] = (int32_t)fo[k];
-    M.hi[k] = (int32_t)(fo[k] + ln[k]);
-    M.src[k] = (k == 4 ? blobs : fields) + so[k];
-  }
-  return true;
-}
-
-// The message's data segments as a per-wave LDS table (4 words each: lo, hi, and the 64-bit
-// source - lo), entry 5 empty, so a lane finds a segment's bounds and source with one ds_read_b128
-// at its own index instead of a select chain over all five (the chain cost ~45 VALU a piece).
-__device__ __forceinline__ void stream_seg_table(const StreamMsg& M, u32x4* tab, uint32_t lane) {
-  __builtin_amdgcn_wave_barrier();  // one wave's LDS operations run in order: keep the program order
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      const uint64_t dl = (uint64_t)M.src[k] - (uint64_t)(int64_t)M.lo[k];
-      tab[k] = u32x4{(uint32_t)M.lo[k], (uint32_t)M.hi[k], (uint32_t)dl, (uint32_t)(dl >> 32)};
-    }
-    tab[5] = u32x4{0u, 0u, 0u, 0u};
-  }
-  __builtin_amdgcn_wave_barrier();
-}
-
-// The source of the 16-B output piece at message-relative dd (dd + m0 a multiple of 16) when the piece
-// lies inside one data segment, else 0. The segments are in message order with lo nondecreasing, so
-// the only one that can hold the piece is the last whose lo <= dd.
-__device__ __forceinline__ uint64_t stream_piece_src(const StreamMsg& M, const u32x4* tab, int32_t dd) {
-  const uint32_t k = (uint32_t)(dd >= M.lo[1]) + (uint32_t)(dd >= M.lo[2]) + (uint32_t)(dd >= M.lo[3]) +
-                     (uint32_t)(dd >= M.lo[4]);
-  const u32x4 e = tab[k];
-  const bool in = dd >= (int32_t)e.x && dd + 16 <= (int32_t)e.y;
-  const uint64_t src = (((uint64_t)e.w << 32) | e.z) + (uint64_t)(int64_t)dd;
-  return in ? src : 0;
-}
-
-// A 16-B load from a source address held as an integer, kept in the global address space (a generic
-// pointer would make it a flat load, which also counts on lgkmcnt, as the stores above).
-__device__ __forceinline__ u32x4 ld16ug(uint64_t a) { return *reinterpret_cast<const gu32x4*>(a); }
-
-constexpr uint32_t kStreamSbs = 2;  // super-blocks a message's runs span: ceil((63 + kStreamPutMax) / 4096)
-static_assert((63 + kStreamPutMax + kSuperBlock - 1) / kSuperBlock <= kStreamSbs, "streamed message spans");
-
-// A wave per message (grid-stride over the waves of one 1024-thread workgroup per CU; the next
-// message's descriptor loaded while this one runs). The message's output is 1 or 2 super-blocks of
-// 4 KiB from its first 64-B run, four 1 KiB wave pieces each. All loads go out first: the source of
-// each piece that lies inside one data segment, and the bytes of each segment whose piece is not
-// inside it (at most 15 at either end; a lane each). Then the stores: those pieces (16 B each) and
-// those edge bytes. Then the remaining pieces that touch the message are loaded back from the output,
-// where put_layout_kernel wrote the gaps' bytes (the header, record prefixes) and this wave the edge
-// bytes -- one wave's lanes, through the CU's one L1: no fence needed. Then, per super-block, the quad
-// transpose and run_crc as region_runs_kernel hashes them, the 64 sums stored (16-B stores of the lanes
-// whose runs overlap the message) into the message's run slots. A run that is not inside the message
-// (its neighbours' bytes), or that holds a CRC field, is never summed: put_stream_seal_kernel re-reads
-// those bytes once every field is written. (Software-pipelining two messages per wave measured slower:
-// 128 VGPRs and spills, 0.79 against 0.70 ms.)
-#if AMBRY_STREAM_PIPE
-// Pipelined across messages: while message i's output is stored, its gap pieces loaded back and its
-// runs hashed, message i+1's source loads are in flight. For the hash to wait only for message i's
-// loads, the loads issued after them must be the same in number on every path (the compiler's wait
-// counts are the least over the paths): so every edge-byte and piece load of the next message is
-// issued, a lane or a message with nothing to load reading the table image instead, and the
-// descriptors are read as dwords through the constant address space (scalar loads; a byte field
-// read from a vector load would wait for every load in flight). Piece sources are not kept: a bit
-// mask per lane says which of the 8 pieces came from a source.
-namespace {
-struct StreamUnit {  // wave-uniform: one message's output and its run slots
-  uint8_t* out;      // the message's first byte
-  int32_t p0b;       // (its first run's start) - (its first byte), <= 0
-  int32_t len;
-  uint32_t nruns;    // 0: no message
-  uint32_t* rk;
-};
-}  // namespace
-
-__global__ __launch_bounds__(1024) void put_stream_kernel(StreamPutArgs a) {
-  fill_lds_slices(a.img);
-  const uint32_t lane = threadIdx.x & 63u;
-  const LaneConst k = make_lane_const(lane);
-  uint32_t* buf = g_lds_runs + kSliceBytes / 4 + (threadIdx.x >> 6) * (kRunsBufBytes / 4);
-  u32x4* const tab = reinterpret_cast<u32x4*>(buf + 128);  // the segment table (words 128..151 of the wave's buffer)
-  const uint32_t slot = 16u * (lane & 3u) + (lane >> 2);
-  const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
-  const uint32_t wave = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) * gridDim.x + blockIdx.x);
-  typedef __attribute__((address_space(4))) const uint32_t cword;
-  static_assert(sizeof(ambrycrc_put_desc) == 80, "descriptor words");
-  auto desc_at = [&](uint64_t j) {
-    cword* w = (cword*)(uintptr_t)a.desc + 20 * j;
-    uint32_t r[20];
-#pragma unroll
-    for (int t = 0; t < 20; ++t) r[t] = w[t];
-    ambrycrc_put_desc d;
-    __builtin_memcpy(&d, r, sizeof d);
-    return d;
-  };
-  const uint64_t dummy = (uint64_t)(uintptr_t)a.img;  // loads with nothing to fetch read the table image
-
-  // The next streamed message from i on (i advances past the job path's and invalid ones): its unit,
-  // segment table, edge bytes and source pieces, every load issued, none waited for.
-  uint64_t i = wave;
-  auto start = [&](StreamUnit& u, int32_t (&ee)[3], uint32_t (&eb)[3], u32x4 (&x)[kStreamSbs][4], uint32_t& pm) {
-    StreamMsg M;
-    ambrycrc_put_desc d{};
-    bool ok = false;
-    for (; i < a.m && !ok; i += nwaves) {
-      d = desc_at(i);
-      ok = stream_msg(d, a.fields, a.blobs, M);  // else the job path's (or invalid: nothing written)
-      if (ok) u.rk = a.rk + kRunPad + i * kStreamPutRuns;
-    }
-    const uint64_t m0 = a.oreg0 + d.out_off, S0 = m0 & ~uint64_t(63);
-    const int32_t mis = (int32_t)(m0 & 15u);
-    u.out = a.obase + m0;
-    u.p0b = (int32_t)(S0 - m0);
-    u.len = ok ? M.len : 0;
-    u.nruns = ok ? (uint32_t)((m0 + M.len - S0 + 63) >> 6) : 0u;
-    if (ok) stream_seg_table(M, tab, lane);
-#pragma unroll
-    for (uint32_t it = 0; it < 3; ++it) {
-      const uint32_t idx = 64 * it + lane, s = idx >> 5, j = idx & 31u;
-      const u32x4 t = tab[s < 5 ? s : 5];
-      const int32_t lo = (int32_t)t.x, hi = (int32_t)t.y;
-      const int32_t up = ((lo + mis + 15) & ~15) - mis, dn = ((hi + mis) & ~15) - mis;
-      const int32_t e = j < 16 ? lo + (int32_t)j : (up > dn ? up : dn) + (int32_t)j - 16;
-      const bool live = ok && s < 5 && (j < 16 ? e < (up < hi ? up : hi) : e < hi);
-      ee[it] = live ? e : -1;
-      eb[it] = *reinterpret_cast<const gu8*>(live ? (((uint64_t)t.w << 32) | t.z) + (uint64_t)(int64_t)e : dummy);
-    }
-    const int32_t p0 = u.p0b + 16 * (int32_t)lane;
-    pm = 0;
-#pragma unroll
-    for (uint32_t sb = 0; sb < kStreamSbs; ++sb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const uint64_t src = ok ? stream_piece_src(M, tab, p0 + (int32_t)(kSuperBlock * sb + kBlockBytes * q)) : 0;
-        x[sb][q] = ld16ug(src ? src : dummy);
-        pm |= src ? 1u << (4 * sb + q) : 0u;
-      }
-    return ok;
-  };
-
-  StreamUnit un;
-  int32_t een[3];
-  uint32_t ebn[3];
-  u32x4 xn[kStreamSbs][4];
-  uint32_t pmn;
-  bool more = start(un, een, ebn, xn, pmn);
-  while (more) {
-    const StreamUnit u = un;
-    int32_t ee[3];
-    uint32_t eb[3];
-    u32x4 x[kStreamSbs][4];
-    const uint32_t pm = pmn;
-#pragma unroll
-    for (int t = 0; t < 3; ++t) ee[t] = een[t], eb[t] = ebn[t];
-#pragma unroll
-    for (uint32_t sb = 0; sb < kStreamSbs; ++sb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) x[sb][q] = xn[sb][q];
-    // this message's stores: the edge bytes, then its source pieces (one base per super-block, shared
-    // with the load-backs below: an address computed between the stores and a load-back would reuse a
-    // stored register and wait for that store to complete)
-    const int32_t p0 = u.p0b + 16 * (int32_t)lane;
-    uint8_t* pb[kStreamSbs] = {u.out + p0, u.out + p0 + kSuperBlock};
-#pragma unroll
-    for (uint32_t sb = 0; sb < kStreamSbs; ++sb) asm volatile("" : "+v"(pb[sb]));  // opaque: kept, not rematerialized
-#pragma unroll
-    for (uint32_t it = 0; it < 3; ++it)
-      if (ee[it] >= 0) st8g(u.out + ee[it], eb[it]);
-#pragma unroll
-    for (uint32_t sb = 0; sb < kStreamSbs; ++sb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (pm & (1u << (4 * sb + q))) st16u_nt(pb[sb] + kBlockBytes * q, x[sb][q]);
-    // its gap pieces loaded back (the layout kernel's bytes and the edge bytes just stored); pieces
-    // outside the message keep what the lane loaded (the table image): the runs they fall in cross the
-    // message's ends or lie outside it, and are never summed
-#pragma unroll
-    for (uint32_t sb = 0; sb < kStreamSbs; ++sb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int32_t dd = p0 + (int32_t)(kSuperBlock * sb + kBlockBytes * q);
-        if (!(pm & (1u << (4 * sb + q))) && dd + 16 > 0 && dd < u.len)
-          x[sb][q] = ld16ug((uint64_t)(uintptr_t)(pb[sb] + kBlockBytes * q));
-      }
-    // the next message's parse and loads, in flight while this one is hashed
-    more = start(un, een, ebn, xn, pmn);
-#pragma unroll
-    for (uint32_t sb = 0; sb < kStreamSbs; ++sb) {
-      if (64 * sb >= u.nruns) break;
-      quad_transpose_asm(x[sb]);
-      buf[slot] = run_crc<4, 1>(x[sb], k, 0u);
-      if (64 * sb + 4 * lane < u.nruns && lane < 16)  // runs 64 sb + 4 lane .. + 3, as region_runs_kernel's stores
-        *reinterpret_cast<u32x4*>(u.rk + 64 * sb + 4 * lane) = *reinterpret_cast<const u32x4*>(buf + 4u * lane);
-    }
-  }
-}
-#else
-__global__ __launch_bounds__(1024) void put_stream_kernel(StreamPutArgs a) {
-  fill_lds_slices(a.img);
-  const uint32_t lane = threadIdx.x & 63u;
-  const LaneConst k = make_lane_const(lane);
-  uint32_t* buf = g_lds_runs + kSliceBytes / 4 + (threadIdx.x >> 6) * (kRunsBufBytes / 4);
-  u32x4* const tab = reinterpret_cast<u32x4*>(buf + 128);  // the segment table (words 128..151 of the wave's buffer)
-  const uint32_t slot = 16u * (lane & 3u) + (lane >> 2);
-  const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
-  const uint32_t wave = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) * gridDim.x + blockIdx.x);
-  ambrycrc_put_desc next{};
-  if (wave < a.m) next = a.desc[wave];
-  for (uint64_t i = wave; i < a.m; i += nwaves) {
-    const ambrycrc_put_desc d = next;
-    if (i + nwaves < a.m) next = a.desc[i + nwaves];
-    StreamMsg M;
-    if (!stream_msg(d, a.fields, a.blobs, M)) continue;  // the job path's (or invalid: nothing written)
-    const uint64_t m0 = a.oreg0 + d.out_off, S0 = m0 & ~uint64_t(63);
-    const int32_t mis = (int32_t)(m0 & 15u);
-    uint8_t* const out = a.obase + m0;
-    // edge bytes: slot j < 16 of segment s is byte lo + j (below the first inside piece), j >= 16 byte
-    // max(first inside piece, last piece's start) + j - 16 (the rest); 32 slots a segment
-    stream_seg_table(M, tab, lane);
-    int32_t ee[3];
-    uint32_t eb[3];
-#pragma unroll
-    for (uint32_t it = 0; it < 3; ++it) {
-      const uint32_t idx = 64 * it + lane, s = idx >> 5, j = idx & 31u;
-      const u32x4 t = tab[s < 5 ? s : 5];
-      const int32_t lo = (int32_t)t.x, hi = (int32_t)t.y;
-      const int32_t up = ((lo + mis + 15) & ~15) - mis, dn = ((hi + mis) & ~15) - mis;
-      const int32_t e = j < 16 ? lo + (int32_t)j : (up > dn ? up : dn) + (int32_t)j - 16;
-      const bool live = s < 5 && (j < 16 ? e < (up < hi ? up : hi) : e < hi);
-      ee[it] = live ? e : -1;
-      eb[it] = live ? (uint32_t)*reinterpret_cast<const gu8*>((((uint64_t)t.w << 32) | t.z) + (uint64_t)(int64_t)e) : 0u;
-    }
-    const int32_t p0 = (int32_t)(S0 - m0) + 16 * (int32_t)lane;
-    u32x4 x[kStreamSbs][4];
-    uint64_t ps[kStreamSbs][4];
-#pragma unroll
-    for (uint32_t sb = 0; sb < kStreamSbs; ++sb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        ps[sb][q] = stream_piece_src(M, tab, p0 + (int32_t)(kSuperBlock * sb + kBlockBytes * q));
-        x[sb][q] = u32x4{0u, 0u, 0u, 0u};
-        if (ps[sb][q]) x[sb][q] = ld16ug(ps[sb][q]);
-      }
-#pragma unroll
-    for (uint32_t it = 0; it < 3; ++it)
-      if (ee[it] >= 0) st8g(out + ee[it], eb[it]);
-#pragma unroll
-    for (uint32_t sb = 0; sb < kStreamSbs; ++sb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (ps[sb][q]) st16u_nt(out + p0 + (int32_t)(kSuperBlock * sb + kBlockBytes * q), x[sb][q]);
-#pragma unroll
-    for (uint32_t sb = 0; sb < kStreamSbs; ++sb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int32_t dd = p0 + (int32_t)(kSuperBlock * sb + kBlockBytes * q);
-        if (!ps[sb][q] && dd + 16 > 0 && dd < M.len) x[sb][q] = *reinterpret_cast<const u32x4*>(out + dd);
-      }
-    const uint64_t nruns = (m0 + M.len - S0 + 63) >> 6;
-    uint32_t* rk = a.rk + kRunPad + i * kStreamPutRuns;
-#pragma unroll
-    for (uint32_t sb = 0; sb < kStreamSbs; ++sb) {
-      if (64 * sb >= nruns) break;
-      quad_transpose_asm(x[sb]);
-      buf[slot] = run_crc<4, 1>(x[sb], k, 0u);
-      if (64 * sb + 4 * lane < nruns && lane < 16)  // runs 64 sb + 4 lane .. + 3, as region_runs_kernel's stores
-        *reinterpret_cast<u32x4*>(rk + 64 * sb + 4 * lane) = *reinterpret_cast<const u32x4*>(buf + 4u * lane);
-    }
-  }
-}
-#endif  // AMBRY_STREAM_PIPE
-
-hipError_t launch_put_stream(const StreamPutArgs& a, int num_cu, hipStream_t s) {
-  return launch_items(put_stream_kernel, a.m ? (uint32_t)num_cu : 0u, 1024, s, a);
-}
-
-size_t stream_put_rk_bytes(size_t m) { return ((kRunPad + (size_t)m * kStreamPutRuns) * sizeof(uint32_t) + 255) & ~size_t(255); }
-
-// ---- region mode in one pass: region_fused_kernel (FusedArgs, crc32_kernels.h) ----
-// Workgroup b (one per CU) owns groups [G0, G1) of 16 KiB (4 super-blocks). Streaming wave v <
-// S = 16 - f.nproc takes groups G0 + v, G0 + v + S, ...: the CU's frontier
-// advances S groups at a time, each wave's 4 super-blocks hashed as region_runs_kernel does them,
-// the next 4 in flight, the 256 run sums stored as one 1 KiB wave store. At the top of each group
-// the wave waits for all its memory operations (the previous group's store included) and publishes
-// how many of its groups are complete in LDS (done[v]).
-// Processor wave p takes 64-message batches p, p + f.nproc, ... of the CU's messages -- those
-// whose offsets lie in the share, found by a 64-way search of the sorted offsets -- waiting on the
-// frontier (the longest complete prefix of the share's groups) first until the batch's headers are
-// streamed, then until its messages' ends are; then region::process_message. A message that
-// starts before the share or ends past it goes to the deferred list for region_tail_kernel.
-// Offsets out of order anywhere set ctl[0], and the tail kernel then redoes every message.
-// Base-relative position of message i's start (past the region: its end).
-__device__ __forceinline__ uint64_t msg_pos(const FusedArgs& f, uint64_t i) {
-  const uint64_t o = f.a.msg_off[i];
-  return f.g.reg0 + (o < f.a.region_len ? o : f.a.region_len);
-}
-
-// Smallest i in [0, m] with msg_pos(i) >= key (sorted offsets), by 64-way probes; every lane
-// gets it. Unsorted offsets give some index in [0, m] (the tail kernel redoes them all).
-__device__ __forceinline__ uint64_t lower_bound_wave(const FusedArgs& f, uint64_t key, uint32_t lane) {
-  uint64_t lo = 0, hi = f.a.m;  // answer in [lo, hi]
-  while (hi - lo > 64) {
-    const uint64_t n = hi - lo;
-    const uint64_t q = lo + n * (lane + 1) / 65;  // lo <= q < hi, increasing with lane
-    const uint64_t ball = __ballot(msg_pos(f, q) >= key);
-    if (ball == 0) {
-      lo = lo + n * 64 / 65 + 1;
-    } else {
-      const uint32_t L = (uint32_t)__builtin_ctzll(ball);
-      const uint64_t qL = lo + n * (L + 1) / 65;
-      const uint64_t qP = L ? lo + n * L / 65 : lo;
-      hi = qL;
-      lo = L ? qP + 1 : lo;
-    }
-  }
-  const uint64_t i = lo + lane;
-  const uint64_t ball = __ballot(i < hi && msg_pos(f, i) < key);
-  return lo + (uint64_t)__popcll(ball);
-}
-
-template <bool COPY, int W>
-__global__ __launch_bounds__(64 * W) void region_fused_kernel(FusedArgs f) {
-  __shared__ uint32_t tbl[1024];
-  __shared__ uint32_t nib[region::kNibTotal];
-  __shared__ uint32_t dn[region::kDirSets * region::kNibWords];
-  __shared__ uint32_t done[16];
-  {  // LDS-DMA of the slice tables (the streamers'), then the processors' compact tables and nibble sets
-    issue_lds_slices(f.g.img);
-    for (uint32_t i = threadIdx.x; i < 1024; i += blockDim.x) {
-      const uint32_t j = i >> 8, b = i & 255u;
-      tbl[i] = f.g.img[(((j >> 1) << 16) | (b << 8) | ((j & 1) << 7)) >> 2];
-    }
-    region::stage_nib(nib, f.g.img);
-    region::stage_direct_nib(dn, f.g.img);
-    if (threadIdx.x < 16) done[threadIdx.x] = 0;
-    __builtin_amdgcn_s_waitcnt(0);
-    __syncthreads();
-  }
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t v = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint64_t G0 = f.ngroups * blockIdx.x / gridDim.x, G1 = f.ngroups * (blockIdx.x + 1) / gridDim.x;
-  const RegionArgs a = f.g;
-  const uint32_t nstream = W - f.nproc;
-  if (v < nstream) {
-    // ---- streaming wave
-    const LaneConst k = make_lane_const(lane);
-    uint32_t* buf = g_lds_runs + kSliceBytes / 4 + v * (kRunsBufBytes / 4);
-    const uint32_t slot = 16u * (lane & 3u) + (lane >> 2);
-    const uint64_t mine = G1 - G0 > v ? (G1 - G0 - v + nstream - 1) / nstream : 0;
-    // COPY: out[0] is region byte msg_off[0] (base-relative `shift`); every piece holding region
-    // bytes is stored at its place, cut to [shift, shift + out_cap)
-    const uint64_t shift = COPY ? a.reg0 + f.a.msg_off[0] : 0;
-    auto copy = [&](uint64_t sb, const u32x4 (&cur)[4]) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const uint64_t p = sb * kSuperBlock + (uint64_t)kBlockBytes * q + 16u * lane;
-        if (p < a.lo16 || p > a.hi16 || p + 16 <= shift) continue;  // no region byte at or after out[0]
-        const uint64_t d0 = p >= shift ? p - shift : 0;               // its first output byte
-        if (d0 >= f.out_cap) continue;
-        if (p >= shift && d0 + 16 <= f.out_cap) {
-          st16u_nt(f.out + (p - shift), cur[q]);  // streamed once: nontemporal
-        } else {  // the piece holding out[0] or out[out_cap - 1]: byte by byte (rare)
-          const u32x4 v = cur[q];
-#pragma unroll 1
-          for (uint32_t b = 0; b < 16; ++b) {
-            const uint32_t w = b < 4 ? v.x : b < 8 ? v.y : b < 12 ? v.z : v.w;
-            if (p + b >= shift && p + b - shift < f.out_cap) st8g(f.out + (p + b - shift), w >> (8 * (b & 3)));
-          }
-        }
-      }
-    };
-    auto hash = [&](uint64_t sb, uint32_t u, u32x4 (&cur)[4]) -> uint32_t {
-      if constexpr (COPY) copy(sb, cur);
-      region_sb_zero(a, sb, lane, cur);
-      quad_transpose_asm(cur);
-      const uint32_t r = run_crc<4, 1>(cur, k, 0u);
-      buf[64u * u + slot] = r;
-      return r;
-    };
-    const uint64_t gfirst = G0 + v, gstep = nstream, mine_n = mine;
-    if (mine_n) {
-      u32x4 b0[4], b1[4], b2[4], b3[4];
-      uint64_t g = gfirst;
-      region_sb_load<AMBRY_FUSED_NT != 0>(a, 4 * g, lane, b0);
-      region_sb_load<AMBRY_FUSED_NT != 0>(a, 4 * g + 1, lane, b1);
-      region_sb_load<AMBRY_FUSED_NT != 0>(a, 4 * g + 2, lane, b2);
-      region_sb_load<AMBRY_FUSED_NT != 0>(a, 4 * g + 3, lane, b3);
-      for (uint64_t j = 0; j < mine_n; ++j, g += gstep) {
-        const uint64_t nx = j + 1 < mine_n ? g + gstep : g;  // the last group re-reads itself
-        // COPY: a message that cannot take the fast path anywhere ends the pass (the general path
-        // redoes the batch); every 8th group, one L2 read
-        if (COPY && (j & 7) == 7 && __hip_atomic_load(f.xfail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-        const uint32_t r0 = hash(4 * g, 0, b0);
-        if (j >= 2) {
-          // Publication of groups 0 .. j - 2 (their run-sum stores were issued before group j's
-          // loads): a workgroup-scope release fence, then the relaxed LDS store of done[v], paired
-          // with the acquire fence after the processors' poll (wait_for) -- release/acquire in the
-          // HIP memory model, the readers being waves of this workgroup. For gfx950 without
-          // threadgroup split the compiler implements it with s_waitcnt lgkmcnt(0) alone: a CU's
-          // vector memory operations go through its L1 in order, so a processor's later load of a
-          // published sum sees the store (ISA diff against the unfenced form: one s_nop became that
-          // wait). No s_waitcnt vmcnt(0), which would also drain the loads in flight.
-          // z = 0, computed from r0, keeps the store after group j's loads have landed.
-          uint32_t z;
-          asm volatile("v_mov_b32 %0, 0" : "=v"(z) : "v"(r0));
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-          __hip_atomic_store(&done[v], (uint32_t)j - 1u + __builtin_amdgcn_readfirstlane(z), __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-        __builtin_amdgcn_s_setprio(3);
-        region_sb_load<AMBRY_FUSED_NT != 0>(a, 4 * nx, lane, b0);
-        __builtin_amdgcn_s_setprio(0);
-        hash(4 * g + 1, 1, b1);
-        __builtin_amdgcn_s_setprio(3);
-        region_sb_load<AMBRY_FUSED_NT != 0>(a, 4 * nx + 1, lane, b1);
-        __builtin_amdgcn_s_setprio(0);
-        hash(4 * g + 2, 2, b2);
-        __builtin_amdgcn_s_setprio(3);
-        region_sb_load<AMBRY_FUSED_NT != 0>(a, 4 * nx + 2, lane, b2);
-        __builtin_amdgcn_s_setprio(0);
-        hash(4 * g + 3, 3, b3);
-        __builtin_amdgcn_s_setprio(3);
-        region_sb_load<AMBRY_FUSED_NT != 0>(a, 4 * nx + 3, lane, b3);
-        __builtin_amdgcn_s_setprio(0);
-        const u32x4 sums = *reinterpret_cast<const u32x4*>(buf + 4u * lane);
-        *(reinterpret_cast<u32x4*>(a.rk + kRunPad + g * 256) + lane) = sums;
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __hip_atomic_store(&done[v], (uint32_t)mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    return;
-  }
-  // ---- processor wave
-  const uint32_t p = v - nstream;
-  const uint64_t s_lo = G0 * kGroupBytes, s_hi = G1 * kGroupBytes;  // the share, base-relative
-  {  // this wave's slice of the global sortedness check
-    const uint64_t waves = (uint64_t)gridDim.x * f.nproc, w = (uint64_t)blockIdx.x * f.nproc + p;
-    const uint64_t c0 = f.a.m * w / waves, c1 = f.a.m * (w + 1) / waves;
-    bool bad = false;
-    for (uint64_t i = c0 + lane; i < c1; i += 64)
-      if (i + 1 < f.a.m && f.a.msg_off[i] > f.a.msg_off[i + 1]) bad = true;
-    if (__ballot(bad) && lane == 0) atomicOr(f.ctl, 1u);
-  }
-  const uint64_t M0 = blockIdx.x == 0 ? 0 : lower_bound_wave(f, s_lo, lane);
-  const uint64_t M1 = blockIdx.x + 1 == gridDim.x ? f.a.m : lower_bound_wave(f, s_hi, lane);
-  // frontier: base-relative end of the longest complete prefix of the share's groups
-  auto frontier = [&]() -> uint64_t {
-    uint64_t q = ~0ull;
-    if (lane < nstream)
-      q = lane + (uint64_t)nstream *
-                     __hip_atomic_load(&done[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const uint64_t w = __shfl_xor(q, o);
-      q = w < q ? w : q;
-    }
-    return G0 * kGroupBytes + (q < G1 - G0 ? q : G1 - G0) * kGroupBytes;
-  };
-  auto wait_for = [&](uint64_t target) {
-    if (target > s_hi) target = s_hi;
-    while (frontier() < target) __builtin_amdgcn_s_sleep(8);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  };
-  for (uint64_t b = M0 + 64 * (uint64_t)p; b < M1; b += 64 * (uint64_t)f.nproc) {
-    if (COPY && __hip_atomic_load(f.xfail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;  // as the streamers
-    const uint64_t i = b + lane;
-    const bool have = i < M1;
-    // The batch is parsed at once (headers, properties, record heads, stored CRCs: region bytes,
-    // there whether streamed or not), then the processor waits until the frontier passes its
-    // messages' ends and assembles their record CRCs: after the last group of a share, only that
-    // last step is left.
-    uint32_t st;
-    uint64_t mend;
-    const region::TabR tr{reinterpret_cast<const uint8_t*>(g_lds_runs), (lane & 31u) << 2};
-    constexpr bool kEnds = COPY ? AMBRY_FUSED_ENDS >= 1 : AMBRY_FUSED_ENDS >= 2;
-    region::FastPre pre{false, 0};  // COPY: the fast path's shape checks, right after the parse
-    region::process_message<kEnds>(f.a, f.g, tbl, tr, nib, have, i, lane, st, mend, [&](uint64_t pos, uint64_t end) -> bool {
-      // the lane's message ends at pos + end (base-relative): before the share, or past it (the
-      // copy form: more than kDirectSpan past it; its records past the share are hashed from the
-      // bytes) -> the tail's. (Measured: the copy form 0.713 -> 0.695 ms per 262,144 4 KiB PUTs;
-      // the verify form 0.385 -> 0.399 ms, so it keeps deferring them.)
-      if (pos < s_lo || pos + end > s_hi + (COPY ? kDirectSpan : 0)) {
-        const uint32_t at = atomicAdd(f.ctl + 1, 1u);
-        if (at < f.a.m) f.defer[at] = (uint32_t)i;  // (unsorted offsets may defer more: ctl[0] covers them)
-        return false;
-      }
-      if constexpr (COPY) pre = region::transform_fast_pre(f, tbl, i, end);
-      return true;
-    }, [&](uint64_t need) { wait_for(need); }, dn, COPY ? s_hi : ~0ull);
-    if constexpr (COPY) region::transform_fast_post(f, st != ~0u, i, st, mend, pre);  // `out` untouched
-  }
-}
-
-// The deferred messages (or, with ctl[0] set, every message) once all run sums exist: one lane
-// per message, 64 per wave, grid-stride over the list.
-template <bool COPY>
-__global__ __launch_bounds__(256) void region_tail_kernel(FusedArgs f) {
-  const bool all = *f.ctl != 0;
-  const uint64_t n = all ? f.a.m : f.ctl[1];
-  if (n == 0) return;
-  if (COPY && all) {  // offsets out of order: not the fast path's layout
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(f.xfail, 1u);
-    return;
-  }
-  const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
-  if (n <= waves && (uint64_t)blockIdx.x * (blockDim.x >> 6) >= n) return;  // no message for this block
-  __shared__ uint32_t tbl[1024];
-  __shared__ uint32_t nib[region::kNibTotal];
-  __shared__ uint32_t dn[region::kDirSets * region::kNibWords];
-  stage_slice_tables(tbl, f.g.img);
-  region::stage_nib(nib, f.g.img);
-  region::stage_direct_nib(dn, f.g.img);
-  __syncthreads();
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t w0 = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (n <= waves) {
-    // Few messages (the share boundaries' deferrals): a wave per message, each short record hashed
-    // by the wave straight from the region (record_crc_direct), a long one (more than 512 runs)
-    // from the run sums (record_crc_runs_wave). Lane 0 alone walking the run sums took 69 us per
-    // 262,144-message transform; a run-sum tree per record with gf2 multiplies, 60 us; a lane per
-    // 4 MiB message, 12 ms for 4,096 of them.
-    for (uint64_t w = w0; w < n; w += waves) {
-      const uint64_t i = all ? w : f.defer[w];
-      uint32_t st;
-      uint64_t mend;
-      region::process_message_direct(f.a, f.g, tbl, nib, dn, i, lane, st, mend, COPY ? nullptr : &f.g.lng);
-      if constexpr (COPY) region::transform_fast(f, tbl, lane == 0, i, st, mend);
-    }
-    return;
-  }
-  for (uint64_t w = w0; 64 * w < n; w += waves) {
-    const uint64_t j = 64 * w + lane;
-    const bool have = j < n;
-    const uint64_t i = have ? (all ? j : f.defer[j]) : 0;
-    uint32_t st;
-    uint64_t mend;
-    region::process_message(f.a, f.g, tbl, region::TabC{tbl}, nib, have, i, lane, st, mend,
-                            [](uint64_t, uint64_t) -> bool { return true; }, [](uint64_t) {}, dn);
-    if constexpr (COPY) region::transform_fast(f, tbl, have, i, st, mend);
-  }
-}
-
-// The transform fast path's last step: with *xfail clear (every message qualified, in the fused
-// and the tail kernel), each message's life version (bytes 2-3) and header CRC (bytes 36-39; 32-35
-// are the stored CRC's zero high word) go into `out` -- after both kernels that wrote `out`'s
-// bytes have completed, so no store of theirs can land after these. One lane per message. Also
-// the device-side verdict for ambrycrc_last_transform_path (path_out).
-__global__ __launch_bounds__(256) void region_patch_kernel(FusedArgs f) {
-  const bool fail = __hip_atomic_load(f.xfail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-  if (f.path_out && blockIdx.x == 0 && threadIdx.x == 0) *f.path_out = fail ? 0u : 1u;
-  if (fail || !f.life) return;
-  const uint64_t off0 = f.a.msg_off[0];
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < f.a.m; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t pt = f.patch[i];
-    uint8_t* o = f.out + (f.a.msg_off[i] - off0);
-    const uint32_t lv = (uint32_t)pt, c = (uint32_t)(pt >> 32);
-    o[2] = (uint8_t)(lv >> 8);
-    o[3] = (uint8_t)lv;
-    o[36] = (uint8_t)(c >> 24);
-    o[37] = (uint8_t)(c >> 16);
-    o[38] = (uint8_t)(c >> 8);
-    o[39] = (uint8_t)c;
-  }
-}
-
-
-hipError_t launch_region_fused(const FusedArgs& f, int num_cu, hipStream_t s) {
-
-  if (f.a.m == 0) return hipSuccess;
-  const bool copy = f.out != nullptr;
-  if (f.ngroups) {
-    if (copy)
-      hipLaunchKernelGGL((region_fused_kernel<true, kFusedWavesCopy>), dim3((uint32_t)num_cu), dim3(64 * kFusedWavesCopy), 0, s, f);
-    else
-      hipLaunchKernelGGL((region_fused_kernel<false, kFusedWavesVerify>), dim3((uint32_t)num_cu), dim3(64 * kFusedWavesVerify),
-                         0, s, f);
-  } else if (hipMemsetAsync(f.ctl, 0xFF, 4, s) != hipSuccess) {  // empty region: all to the tail
-    return hipGetLastError();
-  }
-  // A wave per deferred message whenever there are at most 4 per CU (~1 per share boundary, each
-  // maybe a 4 MiB message whose records a lane alone would walk for milliseconds): blocks without a
-  // message return before staging their tables.
-  const uint32_t blocks = blocks_for(f.a.m, num_cu, 4, 4);
-  if (copy) hipLaunchKernelGGL(region_tail_kernel<true>, dim3(blocks), dim3(256), 0, s, f);
-  else hipLaunchKernelGGL(region_tail_kernel<false>, dim3(blocks), dim3(256), 0, s, f);
-  if (!copy && f.g.lng.ctr) {  // the long records the tail listed, over the whole grid
-    const hipError_t e = launch_region_long(f.a, f.g, num_cu, s);
-    if (e != hipSuccess) return e;
-  }
-  if (copy && (f.life || f.path_out)) {
-    hipLaunchKernelGGL(region_patch_kernel, dim3(f.life ? blocks_for(f.a.m, num_cu, 8) : 1u), dim3(256), 0, s, f);
-  }
-  return hipGetLastError();
-}
-
 hipError_t launch_sweep(const SweepArgs& a, int grid, int num_cu, int variant, hipStream_t s) {
   (void)num_cu;
   switch (variant) {
@@ -2285,242 +1314,6 @@ hipError_t launch_fill(uint8_t* dst, uint64_t nbytes, uint64_t seed, uint64_t st
   if (blocks > 65536) blocks = 65536;
   if (blocks == 0) blocks = 1;
   hipLaunchKernelGGL(fill_splitmix_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, dst, nbytes, seed, stream_off);
-  return hipGetLastError();
-}
-
-// ------------------------------------------------------- read-bandwidth probe
-// Same grid, occupancy and per-lane access pattern as crc32_sweep_kernel (256 KiB
-// tiles per wave, lane l reading bytes [16l, 16l+16) of each KiB, rolling U=8
-// prefetch) with the CRC arithmetic replaced by an XOR: the achievable read roof
-// for this access shape. Variant 1 uses nontemporal loads; variant 2 is a plain
-// grid-stride dwordx4 stream over 8x more, smaller workgroups.
-template <bool NT>
-__global__ __launch_bounds__(1024) void readbw_tiles_kernel(const uint8_t* __restrict__ base, uint64_t nbytes,
-                                                            uint32_t* __restrict__ out) {
-  constexpr int U = 8;
-  constexpr uint64_t kTile = 256u << 10;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-  const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
-  const uint64_t ntiles = nbytes / kTile;
-  uint32_t x = 0;
-  for (uint64_t t = wave; t < ntiles; t += nwaves) {
-    const u32x4* q = reinterpret_cast<const u32x4*>(base + t * kTile) + lane;
-    constexpr uint64_t nb = kTile / kBlockBytes;
-    u32x4 buf[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) buf[u] = ld16<NT>(q + u * 64);
-    for (uint64_t b = 0; b + 2 * U <= nb; b += U) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const u32x4 w = buf[u];
-        buf[u] = ld16<NT>(q + (b + U + u) * 64);
-        x ^= w.x ^ w.y ^ w.z ^ w.w;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) x ^= buf[u].x ^ buf[u].y ^ buf[u].z ^ buf[u].w;
-  }
-  out[blockIdx.x * blockDim.x + threadIdx.x] = x;
-}
-
-// Contiguous per-wave shares (the sweep's layout: share = nbytes / waves, in 1 KiB
-// blocks), optionally entered at a wave-dependent rotation so concurrent waves sit at
-// different offsets of their shares (probes for channel/bank hot spots).
-template <bool ROT>
-__global__ __launch_bounds__(1024) void readbw_share_kernel(const uint8_t* __restrict__ base, uint64_t nbytes,
-                                                            uint32_t* __restrict__ out) {
-  constexpr int U = 8;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) * gridDim.x + blockIdx.x);
-  const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
-  const uint64_t nb = nbytes / kBlockBytes / nwaves;  // blocks per wave
-  const u32x4* q = reinterpret_cast<const u32x4*>(base + (uint64_t)wave * nb * kBlockBytes) + lane;
-  const uint64_t rot = ROT ? ((uint64_t)wave * 97u) % (nb ? nb : 1) : 0;
-  uint32_t x = 0;
-  uint64_t b = 0;
-  for (; b + U <= nb; b += U) {
-    u32x4 w[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      uint64_t bb = b + u + rot;
-      bb = bb >= nb ? bb - nb : bb;
-      w[u] = __builtin_nontemporal_load(q + bb * 64);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) x ^= w[u].x ^ w[u].y ^ w[u].z ^ w[u].w;
-  }
-  out[blockIdx.x * blockDim.x + threadIdx.x] = x;
-}
-
-__global__ __launch_bounds__(256) void readbw_stream_kernel(const u32x4* __restrict__ p, uint64_t n16,
-                                                            uint32_t* __restrict__ out) {
-  constexpr int U = 8;
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  uint32_t x = 0;
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; i + (U - 1) * stride < n16; i += U * stride) {
-    u32x4 w[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) w[u] = __builtin_nontemporal_load(p + i + u * stride);
-#pragma unroll
-    for (int u = 0; u < U; ++u) x ^= w[u].x ^ w[u].y ^ w[u].z ^ w[u].w;
-  }
-  for (; i < n16; i += stride) x ^= p[i].x;
-  out[blockIdx.x * blockDim.x + threadIdx.x] = x;
-}
-
-// The group phase's access shape without its arithmetic: chunks of `chunk` bytes back to back,
-// 64/G per wave round (one per G-lane group), wave w taking an equal run of the chunk list; each
-// lane loads its 16 B of four 16G-byte blocks per 64G-byte super-block (t4_load), one
-// super-block prefetched. The read roof the 4 KiB records' group rounds are compared against.
-// COPY: also store every piece at dst + (its source offset) -- the group phase's copy-through
-// store shape, for the copy roof of that shape (variants 32+ of launch_readbw).
-template <int G, bool COPY = false>
-__global__ __launch_bounds__(1024) void readbw_group_kernel(const uint8_t* __restrict__ base, uint64_t nbytes,
-                                                            uint32_t chunk, uint32_t* __restrict__ out,
-                                                            uint8_t* __restrict__ dst = nullptr) {
-  constexpr uint32_t S = 64 / G;
-  const uint32_t lane = threadIdx.x & 63u, gl = lane & (G - 1), gi = lane / G;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) * gridDim.x + blockIdx.x);
-  const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
-  const uint64_t n = nbytes / chunk;
-  const uint64_t per = ((n + nwaves - 1) / nwaves + S - 1) / S * S;
-  const uint64_t i0 = wave * per, i1 = i0 + per < n ? i0 + per : n;
-  const uint32_t nsb = (chunk + 64 * G - 1) / (64 * G);
-  uint32_t x = 0;
-  for (uint64_t i = i0; i < i1; i += S) {
-    const uint64_t c = i + gi < i1 ? i + gi : i;
-    const u32x4* q = reinterpret_cast<const u32x4*>(base + c * chunk) + gl;
-    u32x4 nx[4], cur[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) nx[j] = ld16<true>(q + G * j);
-    for (uint32_t sb = 0; sb < nsb; ++sb) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        cur[j] = nx[j];
-        if (sb + 1 < nsb) nx[j] = ld16<true>(q + (sb + 1) * 4 * G + G * j);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if constexpr (COPY) {
-          if (sb * 4 * G + G * j + gl < chunk / 16)
-            st16u(dst + c * chunk + 16 * ((uint64_t)sb * 4 * G + G * j + gl), cur[j]);
-        }
-        x ^= cur[j].x ^ cur[j].y ^ cur[j].z ^ cur[j].w;
-      }
-    }
-  }
-  out[blockIdx.x * blockDim.x + threadIdx.x] = x;
-}
-
-// Grid-stride copy over many small blocks (the guide's float4-copy shape): variant 49 plain
-// stores, 50 nontemporal stores.
-template <bool NTS>
-__global__ __launch_bounds__(256) void copybw_gridstride_kernel(const u32x4* __restrict__ src, uint64_t n16,
-                                                               uint8_t* __restrict__ dst) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) {
-    const u32x4 v = ld16<true>(src + i);
-    if constexpr (NTS) st16u_nt(dst + 16 * i, v);
-    else st16u(dst + 16 * i, v);
-  }
-}
-
-// Contiguous copy: each wave copies an equal contiguous share of [0, n16) 16-B pieces, four per
-// lane in flight (the plain copy roof of launch_readbw variant 48).
-__global__ __launch_bounds__(1024) void copybw_stream_kernel(const u32x4* __restrict__ src, uint64_t n16,
-                                                             uint8_t* __restrict__ dst) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint64_t wave = (threadIdx.x >> 6) * (uint64_t)gridDim.x + blockIdx.x;
-  const uint64_t nwaves = (uint64_t)gridDim.x * (blockDim.x >> 6);
-  const uint64_t per = ((n16 + nwaves - 1) / nwaves + 255) / 256 * 256;
-  const uint64_t i0 = wave * per, i1 = i0 + per < n16 ? i0 + per : n16;
-  for (uint64_t i = i0 + lane; i < i1; i += 256) {
-    u32x4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = ld16<true>(src + (i + 64 * u < i1 ? i + 64 * u : i));
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (i + 64 * u < i1) st16u(dst + 16 * (i + 64 * u), v[u]);
-  }
-}
-
-// FETCH_SIZE calibration probe for scattered reads (variants 60 / 61 / 62): every 128-B line of
-// [0, nbytes) is read exactly once, in a scattered order (line = t * odd stride mod lines, lines a
-// power of two), by one 16-B / 4-B / 8-B load at the line start -- the access shape of the message
-// processors' header, field and stored-CRC reads. FETCH_SIZE of a pass over a buffer larger than
-// the Infinity Cache against nbytes gives the multiplier for those reads.
-template <int W>
-__global__ __launch_bounds__(256) void readbw_scatter_kernel(const uint8_t* __restrict__ base, uint64_t lines,
-                                                             uint32_t* __restrict__ out) {
-  uint32_t acc = 0;
-  const uint64_t n = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < lines; t += n) {
-    const uint64_t line = (t * 0x9E3779B1ull) & (lines - 1);
-    const uint8_t* p = base + line * 128;
-    if constexpr (W == 16) {
-      const u32x4 v = *reinterpret_cast<const u32x4*>(p);
-      acc ^= v.x ^ v.y ^ v.z ^ v.w;
-    } else if constexpr (W == 8) {
-      uint64_t v;
-      __builtin_memcpy(&v, p + 3, 8);  // unaligned, as the parse's big-endian long reads
-      acc ^= (uint32_t)v ^ (uint32_t)(v >> 32);
-    } else {
-      acc ^= *reinterpret_cast<const uint32_t*>(p);
-    }
-  }
-  if (acc == 0x9E3779B9u) out[0] = acc;  // keeps the loads
-}
-
-hipError_t launch_readbw(const uint8_t* base, uint64_t nbytes, uint32_t* out, int grid, int variant, hipStream_t s) {
-  if (variant >= 60 && variant <= 62) {
-    uint64_t lines = 1;
-    while (lines * 2 * 128 <= nbytes) lines *= 2;
-    const uint32_t blocks = (uint32_t)grid * 8;
-    if (variant == 60) hipLaunchKernelGGL(readbw_scatter_kernel<16>, dim3(blocks), dim3(256), 0, s, base, lines, out);
-    else if (variant == 61) hipLaunchKernelGGL(readbw_scatter_kernel<4>, dim3(blocks), dim3(256), 0, s, base, lines, out);
-    else hipLaunchKernelGGL(readbw_scatter_kernel<8>, dim3(blocks), dim3(256), 0, s, base, lines, out);
-    return hipGetLastError();
-  }
-  if (variant >= 32) {  // copy probes: read [0, nbytes/2), write from nbytes/2 (+ 11 B for 40..44)
-    const uint64_t half = nbytes / 2 - 4096;
-    uint8_t* dst = const_cast<uint8_t*>(base) + nbytes / 2 + (variant >= 40 && variant < 48 ? 11 : 0);
-    if (variant == 49 || variant == 50) {
-      if (variant == 49)
-        hipLaunchKernelGGL(copybw_gridstride_kernel<false>, dim3(grid * 32), dim3(256), 0, s,
-                           reinterpret_cast<const u32x4*>(base), half / 16, dst);
-      else
-        hipLaunchKernelGGL(copybw_gridstride_kernel<true>, dim3(grid * 32), dim3(256), 0, s,
-                           reinterpret_cast<const u32x4*>(base), half / 16, dst);
-      return hipGetLastError();
-    }
-    if (variant == 48) {
-      hipLaunchKernelGGL(copybw_stream_kernel, dim3(grid), dim3(1024), 0, s, reinterpret_cast<const u32x4*>(base),
-                         half / 16, dst);
-      return hipGetLastError();
-    }
-    if (variant > 44) return hipErrorInvalidValue;  // 45..47, 51+: none
-    const uint32_t chunk = 1024u << ((variant - 32) & 7);
-    hipLaunchKernelGGL((readbw_group_kernel<16, true>), dim3(grid), dim3(1024), 0, s, base, half, chunk, out, dst);
-    return hipGetLastError();
-  }
-  if (variant >= 16) {  // group shape: variant = 16 + log2(chunk bytes / 1024) for G = 16 (4 KiB: 18)
-    const uint32_t chunk = 1024u << (variant - 16);
-    hipLaunchKernelGGL(readbw_group_kernel<16>, dim3(grid), dim3(1024), 0, s, base, nbytes, chunk, out);
-    return hipGetLastError();
-  }
-  switch (variant) {
-    case 0: hipLaunchKernelGGL(readbw_tiles_kernel<false>, dim3(grid), dim3(1024), 0, s, base, nbytes, out); break;
-    case 1: hipLaunchKernelGGL(readbw_tiles_kernel<true>, dim3(grid), dim3(1024), 0, s, base, nbytes, out); break;
-    case 3: hipLaunchKernelGGL(readbw_share_kernel<false>, dim3(grid), dim3(1024), 0, s, base, nbytes, out); break;
-    case 4: hipLaunchKernelGGL(readbw_share_kernel<true>, dim3(grid), dim3(1024), 0, s, base, nbytes, out); break;
-    case 2:
-      hipLaunchKernelGGL(readbw_stream_kernel, dim3(grid * 4 * 8), dim3(256), 0, s,
-                         reinterpret_cast<const u32x4*>(base), nbytes / 16, out);
-      break;
-    default: return hipErrorInvalidValue;
-  }
   return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // msg_parse.h -- one stored message's header, record checks and CRC jobs, for the thread-per-
 // message kernels of the message verify and transform (message_kernels.hip) and the region-mode
-// message processors (crc32_kernels.hip region_fused_kernel / region_tail_kernel).
+// message processors (region_kernels.hip region_fused_kernel / region_tail_kernel).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

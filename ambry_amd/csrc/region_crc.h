@@ -1,5 +1,5 @@
 // region_crc.h -- region mode of the message verify, pass 2: a record's CRC assembled from the
-// 64-B run sums of pass 1 (region_runs_kernel, crc32_kernels.hip), for the fused per-message
+// 64-B run sums of pass 1 (region_runs_kernel, region_kernels.hip), for the fused per-message
 // kernel region_msg_kernel (message_kernels.hip).
 //
 // Why: a region of small PUT messages read as CRC jobs puts every record through

@@ -5,8 +5,8 @@
 // in a region of small messages costs the wave ~1,000 folds instead of one lane ~65,000 dependent
 // Horner steps.
 //
-// Used by region_fused_kernel (crc32_kernels.hip), whose processor waves run beside its streaming
-// waves and take the messages of their CU's share as the share's run sums complete, and by
+// Used by region_fused_kernel (region_kernels.hip, this header's only includer), whose processor
+// waves run beside its streaming waves and take the messages of their CU's share as the share's run sums complete, and by
 // region_tail_kernel, which takes the messages the fused kernel deferred (or all of them when the
 // offsets were not sorted) once every run sum exists.
 #pragma once

@@ -1,4 +1,4 @@
-"""CPU model of the gfx950 sweep kernel (ambry_amd/csrc/crc32_kernels.hip).
+"""CPU model of the gfx950 sweep kernel (ambry_amd/csrc/crc32_kernels.hip over crc_wave.h).
 
 Test infrastructure: it replays the kernel's arithmetic -- the LDS image built
 by libambrycrc (ambrycrc_debug_table_image), v_perm_b32 address formation,
@@ -341,7 +341,7 @@ class KernelModel:
 
 
 class RegionModel:
-    """Region mode of the message verify (crc32_kernels.hip region_runs_kernel, region_crc.h
+    """Region mode of the message verify (region_kernels.hip region_runs_kernel, region_crc.h
     record_crc), scalar: run sums of the 64-B runs from base = region start rounded down
     to 64 B, then each job's CRC from its head / tail runs' bytes, the run sums between, four
     Horner streams and the x^(-8d) un-shift, with the image's one-copy slice tables and nibble
@@ -650,7 +650,7 @@ def gf2_mul(a: int, b: int) -> int:
 
 
 # ---------------------------------------------------------------- put_stream_kernel's partition of a message
-# crc32_kernels.hip: a streamed message's output is cut into 16-B pieces on the destination's 16-B grid
+# put_kernels.hip: a streamed message's output is cut into 16-B pieces on the destination's 16-B grid
 # (mis = m0 & 15; piece t of the two super-blocks starts at message-relative dd = (S0 - m0) + 16 t, S0 = m0
 # rounded down to 64). stream_piece_src stores a piece that lies wholly inside one data segment with one 16-B
 # store; every other segment byte goes through the segment's 32 edge slots, one byte store each. The functions

@@ -4,7 +4,7 @@ assert that coverage with.
 
 Three kernels produce the output bytes of serialize, transform, re-key and send:
 
-  put_stream_kernel (crc32_kernels.hip), copy-mode messages of at most 6,144 B: the output is cut into 16-B
+  put_stream_kernel (put_kernels.hip), copy-mode messages of at most 6,144 B: the output is cut into 16-B
       pieces on the destination's grid; a piece wholly inside a data segment is one 16-B load and store, every
       other segment byte goes through the segment's 32 edge slots. stream_cells().
   the copy-through sweep (SweepArgs::copy_dst, crc32_kernels.hip): every 16-B piece read for a job's CRC is

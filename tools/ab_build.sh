@@ -1,7 +1,10 @@
 #!/bin/bash
 # Build an A/B variant of libambrycrc.so for tools/ab_cases.sh:
 #   tools/ab_build.sh <kernels.hip | -> <name>   ->  build/ab/<name>/libambrycrc.so
-# <kernels.hip> replaces csrc/crc32_kernels.hip ("-": keep the in-tree one). AB_FLAGS adds knob
+# <kernels.hip> replaces csrc/crc32_kernels.hip ("-": keep the in-tree one): the batch engine only
+# (plan, sweep with its group phase, verify, fill). A variant of a region kernel, of the PUT streamer
+# or of a wave primitive (csrc/region_kernels.hip, put_kernels.hip, crc_wave.h) is a patch applied to
+# a scratch tree, or a knob. AB_FLAGS adds knob
 # overrides (-DAMBRY_X=v, csrc/build_knobs.h). Every A/B build is marked a probe build
 # (-DAMBRY_AB_PROBE_BUILD: ambrycrc_version() says so and ambrycrc_init refuses it unless
 # AMBRYCRC_ALLOW_PROBE=1) and carries the split group kernel (variant 32,

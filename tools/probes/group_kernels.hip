@@ -30,6 +30,7 @@
 #include "crc32_gf2.h"
 #include "crc32_kernels.h"
 #include "crc32_layout.h"
+#include "crc_wave.h"  // quad_transpose_asm; this kernel's tables, chain and tree are its own (g2::)
 
 namespace ambrycrc {
 namespace g2 {
@@ -128,40 +129,6 @@ __device__ __forceinline__ uint32_t byte_at(uint32_t b, uint32_t kk, uint32_t la
   if (kk & 4u) v = pow_mul(v, 2);
   if (kk & 8u) v = pow_mul(v, 3);
   return v;
-}
-
-// 4x4 transpose of 16-B elements inside each lane quad (crc32_kernels.hip quad_transpose_asm).
-__device__ __forceinline__ void quad_transpose(u32x4 (&x)[4]) {
-  const uint64_t m1 = 0xAAAAAAAAAAAAAAAAull, n1 = 0x5555555555555555ull;
-  const uint64_t m2 = 0xCCCCCCCCCCCCCCCCull, n2 = 0x3333333333333333ull;
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    uint32_t a0, a1, a2, a3, y0, y1, y2, y3;
-    asm volatile(
-        "s_nop 1\n\t"
-        "s_mov_b64 vcc, %[n1]\n\t"
-        "v_cndmask_b32_dpp %[a0], %[x1], %[x0], vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_dpp %[a2], %[x3], %[x2], vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_mov_b64 vcc, %[m1]\n\t"
-        "v_cndmask_b32_dpp %[a1], %[x0], %[x1], vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_dpp %[a3], %[x2], %[x3], vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_mov_b64 vcc, %[n2]\n\t"
-        "v_cndmask_b32_dpp %[y0], %[a2], %[a0], vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_dpp %[y1], %[a3], %[a1], vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "s_mov_b64 vcc, %[m2]\n\t"
-        "v_cndmask_b32_dpp %[y2], %[a0], %[a2], vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_dpp %[y3], %[a1], %[a3], vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1"
-        : [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3), [y0] "=&v"(y0), [y1] "=&v"(y1),
-          [y2] "=&v"(y2), [y3] "=&v"(y3)
-        : [x0] "v"(x[0][d]), [x1] "v"(x[1][d]), [x2] "v"(x[2][d]), [x3] "v"(x[3][d]), [m1] "s"(m1), [n1] "s"(n1),
-          [m2] "s"(m2), [n2] "s"(n2)
-        : "vcc");
-    x[0][d] = y0;
-    x[1][d] = y1;
-    x[2][d] = y2;
-    x[3][d] = y3;
-  }
 }
 
 // Lane-bit tree level: lanes with bit BIT set absorb the partner's state shifted by POW[POWK].
@@ -398,7 +365,7 @@ __device__ __forceinline__ void class_runs(const SweepArgs& a, uint64_t lo, uint
         if constexpr (COPY) copy_piece(dsh, p, x[q], (int64_t)c.cs);
         fix_piece(x[q], p, c.cs, c.rinit);
       }
-      quad_transpose(x);
+      quad_transpose_asm(x);
       s = run_crc<4>(x, k, sb ? nib_mul(s, kFold) : 0u);
 #pragma unroll
       for (int q = 0; q < 4; ++q) x[q] = nx[q];

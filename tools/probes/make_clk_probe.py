@@ -29,10 +29,10 @@ def main(dst):
     grp = "    if (grp) group_phase_cls<true, COPY>(a, wave, nwaves, lane, make_lane_const(lane));\n"
     s = sub(s, grp, grp + "    if (!COPY && lane == 0 && wave < 8192) {\n      g_probe_clk[wave * 8 + 0] = t_entry;\n"
             "      g_probe_clk[wave * 8 + 1] = t_fill;\n      g_probe_clk[wave * 8 + 2] = clock64();\n    }\n")
-    s = sub(s, "  const uint32_t gi = lane / G;\n#pragma unroll 1\n  for (uint64_t i = i0; i < i1; i += S) {\n"
+    s = sub(s, "  const uint32_t gi = lane / G;\n#pragma unroll 1\n  for (uint64_t i = gr.i0; i < i1; i += gr.stride) {\n"
                "    const bool act = i + gi < i1;",
             "  const uint32_t gi = lane / G;\n  uint64_t p_meta = 0, p_crc = 0, p_store = 0, p_rounds = 0;\n"
-            "#pragma unroll 1\n  for (uint64_t i = i0; i < i1; i += S) {\n    const uint64_t t_a = clock64();\n"
+            "#pragma unroll 1\n  for (uint64_t i = gr.i0; i < i1; i += gr.stride) {\n    const uint64_t t_a = clock64();\n"
             "    const bool act = i + gi < i1;")
     s = sub(s, "    const bool leader = (lane & (G - 1)) == 0 && act;\n    uint64_t stored = 0;",
             "    asm volatile(\"\" ::\"s\"(nbw));\n    const uint64_t t_b = clock64();\n"

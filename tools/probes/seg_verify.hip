@@ -34,7 +34,9 @@
 #include <algorithm>
 #include <vector>
 
-#include "../../ambry_amd/csrc/crc32_kernels.hip"
+#include "../../ambry_amd/csrc/crc32_kernels.h"
+#include "../../ambry_amd/csrc/crc32_layout.h"
+#include "../../ambry_amd/csrc/crc_wave.h"
 #include "../../ambry_amd/csrc/region_crc.h"
 
 #define CK(e)                                                          \
@@ -45,9 +47,6 @@
       exit(1);                                                         \
     }                                                                  \
   } while (0)
-
-// crc32_kernels.hip's host side names pass 2's long-record launcher (message_kernels.hip): unused here.
-hipError_t ambrycrc::launch_region_long(const MsgArgs&, const RegionArgs&, int, hipStream_t) { return hipErrorNotSupported; }
 
 namespace seg {
 using namespace ambrycrc;
