@@ -114,6 +114,15 @@ _SIGNATURES = [
     ("ambrycrc_recover_messages_cpu", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_void_p, ctypes.c_void_p]),
+    ("ambrycrc_ingest_puts_workspace_size", ctypes.c_size_t, [ctypes.c_size_t]),
+    ("ambrycrc_ingest_out_bound", ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_size_t]),
+    ("ambrycrc_ingest_put_requests_dev", ctypes.c_int,
+     [_u8p, ctypes.c_uint64, _u8p, ctypes.c_size_t, ctypes.c_int, _u8p, ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p,
+      _u8p, _u8p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    ("ambrycrc_ingest_put_request_cpu", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+      ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
+      ctypes.POINTER(ctypes.c_uint32)]),
     ("ambrycrc_hard_delete_workspace_bytes", ctypes.c_size_t, [ctypes.c_size_t]),
     ("ambrycrc_hard_delete_messages_dev", ctypes.c_int,
      [_u8p, ctypes.c_uint64, _u8p, ctypes.c_size_t, _u8p, ctypes.c_int, _u8p, _u8p, ctypes.c_void_p, ctypes.c_size_t,

@@ -376,6 +376,39 @@ struct RekeyArgs {
 hipError_t launch_rekey_plan(const RekeyArgs& a, int num_cu, hipStream_t s);
 hipError_t launch_rekey_write(const RekeyArgs& a, int num_cu, hipStream_t s);
 
+// PutRequest ingest (ingest_kernels.hip, ambrycrc_ingest.cpp; the per-request rules: put_request.h):
+// wire frames -> parse and the five CRC jobs a request -> the wire CRC combined from the jobs' CRCs, the
+// verdict and the put descriptor -> placement -> header, record heads, properties and trailers written
+// by one thread per request, bodies by the gather copy.
+struct IngestPlan;  // put_request.h
+struct IngestArgs {
+  const uint8_t* wire;
+  uint64_t wire_len;
+  const ::ambrycrc_put_request_ref* req;  // [m] the caller's
+  uint64_t m;
+  int header_version;                 // of the output
+  IngestPlan* plan;                   // [m] ingest_plan_kernel
+  ::ambrycrc_put_desc* desc;          // [m] ingest_verdict_kernel (header_version 0: nothing to write)
+  uint64_t* job_off;                  // [5m] the CRC jobs over the wire buffer, slot-major (job k*m + i)
+  uint64_t* job_len;                  // [5m]
+  const uint32_t* seg;                // [5m] their CRCs
+  uint64_t* out_len;                  // [m]
+  const uint64_t* out_off;            // [m] the placement's (UINT64_MAX: not placed)
+  uint32_t* status;                   // [m]
+  uint32_t* wire_crc;                 // [m] or null
+  ::ambrycrc_message_info* info;      // [m] or null
+  unsigned long long* total;          // or null: zeroed by ingest_verdict_kernel, raised by ingest_write_kernel
+  uint8_t* out;
+  uint64_t* cp_src;                   // [4m] the copy jobs, slot-major, absolute sources, as CopyArgs
+  uint64_t* cp_dst;
+  uint64_t* cp_len;
+  uint64_t* cp_cost;
+  const uint32_t* img;
+};
+hipError_t launch_ingest_plan(const IngestArgs& a, int num_cu, hipStream_t s);
+hipError_t launch_ingest_verdict(const IngestArgs& a, int num_cu, hipStream_t s);
+hipError_t launch_ingest_write(const IngestArgs& a, int num_cu, hipStream_t s);
+
 // MessageFormatSend (send_kernels.hip, ambrycrc_send.cpp; the per-message rules: send.h): the verify's
 // parse, the encryption-key records' CRCs, then one thread per message decides what is sent and what
 // each of its five verify jobs does, the spans are packed, and the verify's CRC pass copies every sent

@@ -66,14 +66,12 @@ struct MemBytes {
   __host__ __device__ bool ascii(uint64_t i, uint64_t n) const { return bytes_ascii(p + i, n); }
 };
 
-// BlobPropertiesSerDe.getBlobPropertiesFromStream over the n bytes at s (the record's payload:
-// its span minus the 2-B record version and the 8-B CRC). 0, or AMBRYCRC_MSG_BAD_RECORD when a
-// read throws (unknown SerDe version, a negative string size, a field past the span --
-// BlobProperties_Format_V1.deserializeBlobPropertiesRecord maps each to DataCorrupt,
-// MessageFormatRecord.java:1192-1195) or the fields end before the span does (the reference would
-// take other bytes for the CRC). ASCII: also scan the string bytes (the transform's question).
+// BlobPropertiesSerDe.getBlobPropertiesFromStream reading from s with at most n bytes to take (the
+// open-ended form: a PutRequest's properties carry no length, PutRequest.java:449): 0 and *end = where
+// the fields end, or AMBRYCRC_MSG_BAD_RECORD when a read throws (unknown SerDe version, a negative
+// string size, a field past the n bytes). ASCII: also scan the string bytes (the transform's question).
 template <bool ASCII, class B>
-__host__ __device__ inline uint32_t props_parse_b(const B& s, uint64_t n, PropsFields* f) {
+__host__ __device__ inline uint32_t props_walk_b(const B& s, uint64_t n, PropsFields* f, uint64_t* end) {
   if (n < kSerdeFixed) return AMBRYCRC_MSG_BAD_RECORD;
   const int32_t v = (int16_t)s.be16(0);
   if (v < 1 || v > 5) return AMBRYCRC_MSG_BAD_RECORD;  // "stream has unknown blob property version"
@@ -114,6 +112,20 @@ __host__ __device__ inline uint32_t props_parse_b(const B& s, uint64_t n, PropsF
     if (pos > n) return AMBRYCRC_MSG_BAD_RECORD;
   }
   f->ascii = ascii;
+  *end = pos;
+  return 0;
+}
+
+// The same over the n bytes at s that are a record's payload (its span minus the 2-B record version
+// and the 8-B CRC): also AMBRYCRC_MSG_BAD_RECORD when a read throws -- there
+// BlobProperties_Format_V1.deserializeBlobPropertiesRecord maps each to DataCorrupt
+// (MessageFormatRecord.java:1192-1195) -- or the fields end before the span does (the reference
+// would take other bytes for the CRC).
+template <bool ASCII, class B>
+__host__ __device__ inline uint32_t props_parse_b(const B& s, uint64_t n, PropsFields* f) {
+  uint64_t pos = 0;
+  const uint32_t st = props_walk_b<ASCII>(s, n, f, &pos);
+  if (st) return st;
   return pos == n ? 0u : AMBRYCRC_MSG_BAD_RECORD;
 }
 

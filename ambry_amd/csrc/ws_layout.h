@@ -19,6 +19,7 @@
 #include "crc32_kernels.h"
 #include "hard_delete.h"
 #include "put_layout.h"
+#include "put_request.h"
 #include "record_fields.h"
 #include "recover.h"
 #include "rekey.h"
@@ -214,6 +215,28 @@ inline RekeyOwn rekey_own(Carver& c, size_t m, RekeyArgs& a) {
   return w;
 }
 inline size_t rekey_own_bytes(size_t m) { return measure(rekey_own, m); }
+
+// ------------------------------------------------------------ ingest
+// Put descriptors, the parse's plans, the kIngestSegs CRC jobs a request (off, len) and the kIngestSlots
+// copy jobs (src, dst, len, cost), then the jobs' CRCs, the placement scan's per-request output and the
+// copy scan's per-job output. Walked under ASan + UBSan by tests/native/ingest_ws_asan.cpp.
+struct IngestOwn {
+  uint32_t *seg, *scan_out, *cp_scan_out;  // seg: a.seg, writable
+};
+inline IngestOwn ingest_own(Carver& c, size_t m, IngestArgs& a) {
+  IngestOwn w;
+  a.desc = c.take<ambrycrc_put_desc>(m);
+  a.plan = c.take<IngestPlan>(m);
+  c.take_each((size_t)kIngestSegs * m, a.job_off, a.job_len);
+  c.take_each((size_t)kIngestSlots * m, a.cp_src, a.cp_dst, a.cp_len, a.cp_cost);
+  w.seg = c.take<uint32_t>((size_t)kIngestSegs * m);
+  a.seg = w.seg;
+  w.scan_out = c.take<uint32_t>(m);
+  w.cp_scan_out = c.take<uint32_t>((size_t)kIngestSlots * m);
+  c.align(256);
+  return w;
+}
+inline size_t ingest_own_bytes(size_t m) { return measure(ingest_own, m); }
 
 // ------------------------------------------------------------ send
 // Span lengths, message ends, the kSendSlots copy destinations a message, the plain-copy jobs (src, dst,

@@ -318,6 +318,88 @@ def rekey_dev(region, msg_off, descs, aux, header_version: int = 3, life_version
     return out, out_off, out_len, status
 
 
+# ------------------------------------------------------------------ PutRequest ingest (AmbryRequests.handlePutRequest)
+# numpy mirror of struct ambrycrc_put_request_ref (16 bytes): one frame of a wire buffer.
+PUT_REQUEST_REF_DTYPE = np.dtype([("off", "<u8"), ("key_len", "<u4"), ("reserved", "<u4")])
+assert PUT_REQUEST_REF_DTYPE.itemsize == 16
+
+MSG_WIRE_CRC = 1 << 17   # AMBRYCRC_MSG_WIRE_CRC: "CRC mismatch, data in PutRequest is unreliable"
+INGEST_GROWTH_MAX = 72   # AMBRYCRC_INGEST_GROWTH_MAX
+
+
+def ingest_out_bound(wire_len: int, m: int) -> int:
+    """ambrycrc_ingest_out_bound: an output capacity that never yields MSG_NO_ROOM for m frames that share no
+    wire bytes."""
+    return int(lib().ambrycrc_ingest_out_bound(wire_len, m))
+
+
+def ingest_workspace_size(m: int) -> int:
+    return int(lib().ambrycrc_ingest_puts_workspace_size(m))
+
+
+def ingest_put_request_cpu(wire, off: int, key_len: int, header_version: int = 3, out_cap=None, reserved: int = 0):
+    """ambrycrc_ingest_put_request_cpu: PutRequest.readFrom and getMessageFormatWriteSet for the frame at `off`
+    of a host buffer whose serialized blob id is key_len bytes long.
+    Returns (status bits, the stored message or None when refused, the computed wire CRC, its MESSAGE_INFO
+    record)."""
+    from .device import _recover_dtypes
+
+    buf = np.frombuffer(wire, dtype=np.uint8) if not isinstance(wire, np.ndarray) else wire
+    ref = np.zeros(1, dtype=PUT_REQUEST_REF_DTYPE)
+    ref[0] = (off, key_len, reserved)
+    cap = out_cap if out_cap is not None else ingest_out_bound(buf.size, 1)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    info = np.zeros(1, dtype=_recover_dtypes()[0])
+    st, crc, n = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
+    check(lib().ambrycrc_ingest_put_request_cpu(ctypes.c_void_p(buf.ctypes.data if buf.size else 0), buf.size,
+                                                ctypes.c_void_p(ref.ctypes.data), header_version,
+                                                ctypes.c_void_p(out.ctypes.data), cap, ctypes.byref(n),
+                                                ctypes.c_void_p(info.ctypes.data), ctypes.byref(crc),
+                                                ctypes.byref(st)),
+          "ambrycrc_ingest_put_request_cpu")
+    return st.value, (out[:n.value].tobytes() if st.value == 0 else None), crc.value, info[0]
+
+
+def ingest_put_requests_dev(wire, refs, header_version: int = 3, out=None, stream=None, workspace=None):
+    """ambrycrc_ingest_put_requests_dev -- AmbryRequests.handlePutRequest for a batch of PutRequest frames in
+    HBM: every frame parsed, its wire CRC checked, and the clean ones written as stored PUT messages at
+    `header_version`, packed in request order into `out` (default: ingest_out_bound bytes). wire: a uint8
+    CUDA tensor; refs: a uint8 CUDA tensor holding the PUT_REQUEST_REF_DTYPE array. workspace: a CUDA tensor
+    of ingest_workspace_size(m) bytes (needed to capture the call into a graph), or None for the stream's
+    default one.
+    Returns (out, out_off int64[m] (-1: not written), out_len int64[m], info uint8[m, 48] (rows of
+    MESSAGE_INFO, zero unless the status is 0), wire_crc int32[m], total int64[1], status int32[m])."""
+    import torch
+
+    from .device import _stream_handle, _workspace
+
+    if wire.dtype != torch.uint8 or not wire.is_cuda or not wire.is_contiguous():
+        raise TypeError("wire must be a contiguous uint8 CUDA tensor")
+    dev = wire.device
+    if refs.dtype != torch.uint8 or not refs.is_cuda or not refs.is_contiguous() or refs.device != dev or \
+            refs.numel() % PUT_REQUEST_REF_DTYPE.itemsize:
+        raise TypeError("refs must be a contiguous uint8 CUDA tensor of 16-byte request references")
+    m = refs.numel() // PUT_REQUEST_REF_DTYPE.itemsize
+    if out is None:
+        out = torch.empty(ingest_out_bound(wire.numel(), m), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.device != dev:
+        raise TypeError("out must be a contiguous uint8 CUDA tensor on the wire buffer's device")
+    out_off = torch.empty(m, dtype=torch.int64, device=dev)
+    out_len = torch.empty(m, dtype=torch.int64, device=dev)
+    info = torch.empty((m, 48), dtype=torch.uint8, device=dev)
+    wire_crc = torch.empty(m, dtype=torch.int32, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    status = torch.empty(m, dtype=torch.int32, device=dev)
+    ws, ws_bytes = _workspace(workspace, dev)
+    ptr = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    check(lib().ambrycrc_ingest_put_requests_dev(ptr(wire), wire.numel(), ptr(refs), m, header_version, ptr(out),
+                                                 out.numel(), ptr(out_off), ptr(out_len), ptr(info), ptr(wire_crc),
+                                                 ptr(total), ptr(status), ws, ws_bytes,
+                                                 ctypes.c_void_p(_stream_handle(stream))),
+          "ambrycrc_ingest_put_requests_dev")
+    return out, out_off, out_len, info, wire_crc, total, status
+
+
 # ------------------------------------------------------------------ serving a GET (MessageFormatSend)
 # MessageFormatFlags ordinals (AMBRYCRC_SEND_*)
 SEND_BLOB_PROPERTIES = 0

@@ -589,6 +589,84 @@ int ambrycrc_recover_messages_cpu(const uint8_t* region, uint64_t region_len, ui
                                   uint64_t* msg_off, ambrycrc_message_info* info, uint32_t* status,
                                   ambrycrc_recover_result* result);
 
+/* ------------------------------------- PutRequest ingest: wire frames to stored PUT messages */
+
+/* One PutRequest frame of a wire buffer. The store key stays opaque: `new BlobId(stream, clusterMap)`
+ * needs the cluster map, so the caller supplies the serialized blob id's length. 16 bytes. */
+typedef struct ambrycrc_put_request_ref {
+  uint64_t off;        /* frame start (its size long) in the wire buffer */
+  uint32_t key_len;    /* serialized BlobId length */
+  uint32_t reserved;   /* 0 */
+} ambrycrc_put_request_ref;
+
+/* "CRC mismatch, data in PutRequest is unreliable" (PutRequest.java:458-460). */
+#define AMBRYCRC_MSG_WIRE_CRC (1u << 17)
+
+/* A stored message is at most this much longer than the frame it comes from. Message overheads:
+ * header V3 40, encryption-key record 2 + 4 + 8, properties record 2 + 8 and the 17-byte appendix of a
+ * SerDe V1 payload re-encoded at VERSION_5, user-metadata record 2 + 4 + 8, blob record 13 + 8: 116.
+ * Frame overheads around the same fields: size, type, version, correlationId and clientIdLen 20 (every
+ * frame has them; an empty client id adds nothing), umSize 4, blobType 2, encKeyLen 2 (the key record
+ * exists only for a V4 / V5 request), blobSize 8, CRC 8: 44. 116 - 44 = 72, reached by a V4 request with
+ * an encryption key, SerDe V1 properties and an empty client id at header V3. */
+#define AMBRYCRC_INGEST_GROWTH_MAX 72
+
+/* AmbryRequests.handlePutRequest for m frames of [d_wire, d_wire + wire_len): PutRequest.readFrom
+ * (PutRequest.java:191-204, :440-521), then getMessageFormatWriteSet (AmbryRequests.java:1957-1970)
+ * through PutMessageFormatInputStream (:60-124). The frame is RequestOrResponse.writeHeader +
+ * PutRequest.prepareBuffer's, every integer big-endian:
+ *   long size | short type | short version | int correlationId | int clientIdLen, clientId |
+ *   [ blobId (key_len bytes) | BlobPropertiesSerDe bytes (V1..V5) | int umSize, userMetadata |
+ *     short blobType | (V4, V5) short encKeyLen, encKey | (V5) byte isCompressed | long blobSize | blob ] | long crc
+ * with the CRC-32 of the bracketed bytes as a long. Per request, the first refusal that applies:
+ *  1. AMBRYCRC_MSG_BAD_DESC: off or the frame's 20-byte fixed part outside the wire buffer; size below the
+ *     smallest frame readFrom accepts (81: a V3 request of SerDe V1 properties with everything empty);
+ *     off + size > wire_len; reserved != 0.
+ *  2. AMBRYCRC_MSG_NOT_PUT: type is not RequestOrResponseType.PutRequest's ordinal (0).
+ *  3. AMBRYCRC_MSG_BAD_VERSION: version not 3, 4 or 5.
+ *  4. AMBRYCRC_MSG_BAD_RECORD: a read of readFrom throws or would pass off + size -- clientIdLen negative or
+ *     overrunning, key_len overrunning, the properties (SerDe version not 1..5, a negative or overrunning
+ *     string size), umSize negative or overrunning, blobType not 0 or 1, encKeyLen negative or overrunning,
+ *     blobSize negative, above Integer.MAX_VALUE or overrunning, no 8 bytes left for the CRC. Bytes between
+ *     the CRC's end and off + size are not looked at.
+ *  5. AMBRYCRC_MSG_WIRE_CRC: the computed CRC differs from the stored long, high word included.
+ *  6. AMBRYCRC_MSG_NOT_ENCODABLE: a BlobProperties string holds a non-ASCII byte (the transform's condition).
+ *  7. AMBRYCRC_MSG_BAD_INFO: creation time below -1.
+ *  8. AMBRYCRC_MSG_BAD_RECORD: a record offset of the message would pass a Java int.
+ *  9. AMBRYCRC_MSG_NO_ROOM: the message does not fit in out_cap; the running offset still advances, as in
+ *     the transform.
+ * The clean requests' messages are packed in request order into [d_out, d_out + out_cap), each what
+ * PutMessageFormatInputStream writes at header_version (1..3; V1 drops the encryption key): life version 0,
+ * the blob id verbatim, the encryption-key record when encKeyLen > 0, the properties at VERSION_5 (canonical
+ * private / encrypted bytes, the defaults of older versions appended), the user metadata, and a
+ * Blob_Format_V3 record of the wire's blob type and isCompressed == 1 (false for V3 / V4 requests). A
+ * refused request takes no room: d_out_len[i] = 0, d_out_off[i] = UINT64_MAX. *d_total = the end of the
+ * last placed message, or 0. d_wire_crc[i] = the computed wire CRC (MessageInfo.crc,
+ * AmbryRequests.java:1968), 0 where the parse was refused. d_info[i], where the status is 0, is what
+ * ambrycrc_recover_messages_dev reports for the message in the written region (msg_off = d_out_off[i]);
+ * zero elsewhere. Every wire byte is hashed once: the wire CRC and the records' CRCs both follow from the
+ * CRCs of the five segments. d_out must not overlap d_wire; bytes of d_out outside the returned spans are
+ * unspecified, and nothing is written when every request is refused.
+ * ambrycrc_ingest_out_bound(wire_len, m) = wire_len + m * AMBRYCRC_INGEST_GROWTH_MAX (saturating): an out_cap
+ * that never yields AMBRYCRC_MSG_NO_ROOM for frames that share no wire bytes.
+ * Only enqueues on `stream`, never synchronizes; may be captured into a HIP graph with a caller workspace
+ * (d_ws >= ambrycrc_ingest_puts_workspace_size(m)); d_ws NULL uses the stream's default workspace.
+ * The size function is deliberately not named *_workspace_bytes: that suffix is the set of layouts
+ * tests/test_workspace_layout.py enumerates, and this one is pinned by tests/golden/ingest_workspace_size.json. */
+size_t   ambrycrc_ingest_puts_workspace_size(size_t m);
+uint64_t ambrycrc_ingest_out_bound(uint64_t wire_len, size_t m);
+int ambrycrc_ingest_put_requests_dev(const uint8_t* d_wire, uint64_t wire_len,
+                                     const ambrycrc_put_request_ref* d_req, size_t m, int header_version,
+                                     uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, uint64_t* d_out_len,
+                                     ambrycrc_message_info* d_info /* nullable */, uint32_t* d_wire_crc /* nullable */,
+                                     uint64_t* d_total /* nullable */, uint32_t* d_status,
+                                     void* d_ws, size_t ws_bytes, hipStream_t stream);
+/* The same for one frame of a wire buffer in host memory (the CLMUL loop for every CRC). info, wire_crc:
+ * nullable. info->msg_off is 0. A message longer than out_cap (or out NULL) gets AMBRYCRC_MSG_NO_ROOM. */
+int ambrycrc_ingest_put_request_cpu(const uint8_t* wire, uint64_t wire_len, const ambrycrc_put_request_ref* req,
+                                    int header_version, uint8_t* out, uint64_t out_cap, uint64_t* out_len,
+                                    ambrycrc_message_info* info, uint32_t* wire_crc, uint32_t* status);
+
 /* ------------------------------------- CRC-trailered records (store files, headers) */
 
 /* Item i = [off[i], off[i] + len[i]) ends in the big-endian 8-B CRC (a long, high word zero)
