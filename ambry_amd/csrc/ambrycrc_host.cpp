@@ -250,36 +250,32 @@ int host_ctx(int device, DevCtx** c) {
   return device >= 0 && !*c ? AMBRYCRC_ENOINIT : AMBRYCRC_OK;
 }
 
-uint32_t rd_be32(const uint8_t* p) {
-  return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-uint64_t rd_be64(const uint8_t* p) { return ((uint64_t)rd_be32(p) << 32) | rd_be32(p + 4); }
-
 // The sizes a message header (versions 1-3) at p gives, unchecked: the header's own length h, the
-// records' total size and the first record's offset from p (-1: the header names no record).
-// False for another version or fewer than h bytes in `rem`. Always inlined: the callers walk
-// hundreds of thousands of headers, a cache miss each, and the misses of successive messages overlap
-// only as far as the core's reorder window reaches -- a call and a struct through memory per
-// message cost the serial scan a fifth of its rate.
+// records' total size and the first record's offset from p (-1: the header names no record). False for
+// another version or fewer than h bytes in `rem`. msg_header.h's decoder, kept written out for the two
+// serial scans below: they walk hundreds of thousands of headers, a cache miss each, and the misses of
+// successive messages overlap only as far as the core's reorder window reaches. Through the shared
+// decoder (its struct, its CRC verdict before the fields) ambrycrc_chain_messages_host ran a tenth
+// slower; the header lattice tests hold this copy to the shared rule.
 struct HeaderSizes {
   uint32_t h;
   int64_t total, first;
 };
 __attribute__((always_inline)) inline bool header_sizes(const uint8_t* p, uint64_t rem, HeaderSizes* s) {
-  const int v = (int16_t)(((uint32_t)p[0] << 8) | p[1]);
-  s->h = v == 1 ? 34u : v == 2 ? 38u : v == 3 ? 40u : 0u;
+  const int v = (int16_t)ld_be16(p);
+  s->h = msg_header_size(v);
   if (s->h == 0 || rem < s->h) return false;
   int32_t rel[kMsgSlots];
   if (v == 1) {
-    s->total = (int64_t)rd_be64(p + 2);
+    s->total = (int64_t)ld_be64(p + 2);
     rel[0] = -1;
-    for (int k = 0; k < 4; ++k) rel[k + 1] = (int32_t)rd_be32(p + 10 + 4 * k);
+    for (int k = 0; k < 4; ++k) rel[k + 1] = (int32_t)ld_be32(p + 10 + 4 * k);
   } else if (v == 2) {
-    s->total = (int64_t)rd_be64(p + 2);
-    for (int k = 0; k < 5; ++k) rel[k] = (int32_t)rd_be32(p + 10 + 4 * k);
+    s->total = (int64_t)ld_be64(p + 2);
+    for (int k = 0; k < kMsgSlots; ++k) rel[k] = (int32_t)ld_be32(p + 10 + 4 * k);
   } else {
-    s->total = (int64_t)rd_be64(p + 4);
-    for (int k = 0; k < 5; ++k) rel[k] = (int32_t)rd_be32(p + 12 + 4 * k);
+    s->total = (int64_t)ld_be64(p + 4);
+    for (int k = 0; k < kMsgSlots; ++k) rel[k] = (int32_t)ld_be32(p + 12 + 4 * k);
   }
   s->first = -1;
   for (int k = 0; k < kMsgSlots; ++k)
@@ -932,7 +928,7 @@ void release_slabs(DevCtx* c) {
 uint64_t message_extent_of(const uint8_t* p, uint64_t rem) {
   const uint64_t hdr = std::min<uint64_t>(rem, 40);
   if (rem < 2) return rem;
-  HeaderSizes s;
+  HeaderSizes s;  // msg_header.h's extent rule: no CRC, any first offset >= 0
   if (!header_sizes(p, rem, &s) || s.total <= 0 || s.first < 0 || (uint64_t)s.total > rem ||
       (uint64_t)s.first > rem - (uint64_t)s.total)
     return hdr;
@@ -1040,7 +1036,7 @@ int ambrycrc_verify_trailed_host(const void* const* ptrs, const uint64_t* lens, 
   const int rc = ambrycrc_batch_host(ptrs, body.data(), nullptr, crc.data(), n, device, pinned);
   if (rc) return rc;
   for (size_t i = 0; i < n; ++i)
-    mismatch[i] = lens[i] < 8 || rd_be64(static_cast<const uint8_t*>(ptrs[i]) + body[i]) != (uint64_t)crc[i];
+    mismatch[i] = lens[i] < 8 || ambrycrc::ld_be64(static_cast<const uint8_t*>(ptrs[i]) + body[i]) != (uint64_t)crc[i];
   return AMBRYCRC_OK;
 }
 
@@ -1084,12 +1080,12 @@ size_t ambrycrc_chain_messages_host(const uint8_t* region, uint64_t region_len, 
   if (!region || !offs) return 0;
   size_t cnt = 0;
   uint64_t off = start;
-  while (cnt < max && off < region_len && region_len - off >= 2) {
+  while (cnt < max && off < region_len && region_len - off >= 2) {  // msg_header.h's chain acceptance
     const uint8_t* p = region + off;
     const uint64_t rem = region_len - off;
     HeaderSizes s;
     if (!header_sizes(p, rem, &s)) break;
-    if ((uint64_t)ambrycrc_update(0, p, s.h - 8) != rd_be64(p + s.h - 8)) break;
+    if ((uint64_t)ambrycrc_update(0, p, s.h - 8) != ld_be64(p + s.h - 8)) break;
     if (s.total <= 0 || s.first < (int64_t)s.h || (uint64_t)s.total > rem || (uint64_t)s.first > rem - (uint64_t)s.total)
       break;
     offs[cnt++] = off;

@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "hard_delete.h"
+#include "msg_header.h"
 #include "put_layout.h"
 #include "record_fields.h"
 #include "recover.h"
@@ -18,106 +19,39 @@
 
 namespace {
 
-uint32_t rd16(const uint8_t* p) { return (uint32_t)p[0] << 8 | p[1]; }
-uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
-uint64_t rd64(const uint8_t* p) { return (uint64_t)rd32(p) << 32 | rd32(p + 4); }
+using ambrycrc::ld_be16;
+using ambrycrc::ld_be32;
+using ambrycrc::ld_be64;
+using ambrycrc::record_check;
 
-constexpr uint32_t kRecordBit[5] = {AMBRYCRC_MSG_ENCKEY_CRC, AMBRYCRC_MSG_PROPS_CRC, AMBRYCRC_MSG_UPDATE_CRC,
+constexpr uint32_t kRecordBit[ambrycrc::kMsgSlots] = {AMBRYCRC_MSG_ENCKEY_CRC, AMBRYCRC_MSG_PROPS_CRC, AMBRYCRC_MSG_UPDATE_CRC,
                                     AMBRYCRC_MSG_USERMETA_CRC, AMBRYCRC_MSG_BLOB_CRC};
 
-// The record-level reads of each deserializer before its CRC (message_kernels.hip record_check).
-uint32_t record_check(int k, const uint8_t* q, uint64_t span) {
-  if (span < 10) return AMBRYCRC_MSG_BAD_RECORD;
-  const uint32_t v = rd16(q);
-  switch (k) {
-    case 0:
-    case 3: {
-      if (v != 1) return AMBRYCRC_MSG_BAD_VERSION;
-      if (span < 14) return AMBRYCRC_MSG_BAD_RECORD;
-      const int32_t n = (int32_t)rd32(q + 2);
-      return n >= 0 && (uint64_t)n + 14 == span ? 0u : AMBRYCRC_MSG_BAD_RECORD;
-    }
-    case 1:
-      return ambrycrc::props_record_check(q, span);
-    case 2:
-      return ambrycrc::update_record_check(q, span);
-    default: {
-      if (v < 1 || v > 3) return AMBRYCRC_MSG_BAD_VERSION;
-      const uint32_t head = v == 1 ? 10u : v == 2 ? 12u : 13u;
-      if (span < head + 8) return AMBRYCRC_MSG_BAD_RECORD;
-      const uint32_t type = v == 1 ? 0u : rd16(q + 2);
-      const uint64_t size = rd64(q + (v == 1 ? 2 : v == 2 ? 4 : 5));
-      return type < 2 && size <= 0x7FFFFFFFull && size + head + 8 == span ? 0u : AMBRYCRC_MSG_BAD_RECORD;
-    }
-  }
+// msg_header.h's field source and CRC for a header in host memory (the CLMUL loop).
+struct HostCrc {
+  const uint8_t* p;
+  uint32_t operator()(uint32_t n) const { return ambrycrc_update(0, p, n); }
+};
+uint32_t decode(const uint8_t* p, uint64_t rem, ambrycrc::MsgHeader* H) {
+  return ambrycrc::msg_decode(ambrycrc::HeaderBytes{p}, rem, HostCrc{p}, H);
 }
 
-struct Parsed {
-  uint32_t version, hsize, life;
-  int64_t total;
-  int32_t rel[5];  // encryption key, properties, update, user metadata, blob; -1 absent
-  uint64_t end;    // message end, relative
-};
-
-// Header and every record of the message at p (rem bytes available): status bits.
-uint32_t verify(const uint8_t* p, uint64_t rem, Parsed* m) {
-  m->end = 0;
-  if (rem < 2) return AMBRYCRC_MSG_BAD_LAYOUT;
-  const int v = (int16_t)rd16(p);
-  const uint32_t h = v == 1 ? 34u : v == 2 ? 38u : v == 3 ? 40u : 0u;
-  if (h == 0) return AMBRYCRC_MSG_BAD_VERSION;
-  if (rem < h) return AMBRYCRC_MSG_BAD_LAYOUT;
-  if ((uint64_t)ambrycrc_update(0, p, h - 8) != rd64(p + h - 8)) return AMBRYCRC_MSG_HEADER_CRC;  // verifyHeader
-  m->version = (uint32_t)v;
-  m->hsize = h;
-  m->life = 0;
-  if (v == 3) {
-    if ((int16_t)rd16(p + 2) < 0) return AMBRYCRC_MSG_BAD_LAYOUT;  // checkHeaderConstraints
-    m->life = rd16(p + 2);
-    m->total = (int64_t)rd64(p + 4);
-    for (int k = 0; k < 5; ++k) m->rel[k] = (int32_t)rd32(p + 12 + 4 * k);
-  } else {
-    m->total = (int64_t)rd64(p + 2);
-    const uint8_t* q = p + 10;
-    if (v == 1) {
-      m->rel[0] = -1;
-      for (int k = 0; k < 4; ++k) m->rel[k + 1] = (int32_t)rd32(q + 4 * k);
-    } else {
-      for (int k = 0; k < 5; ++k) m->rel[k] = (int32_t)rd32(q + 4 * k);
-    }
-  }
-  const int32_t* rel = m->rel;
-  const bool is_put = rel[1] != -1 && rel[2] == -1 && rel[3] != -1 && rel[4] != -1;
-  const bool is_upd = rel[2] != -1 && rel[0] == -1 && rel[1] == -1 && rel[3] == -1 && rel[4] == -1;
-  if (m->total <= 0 || !(is_put || is_upd)) return AMBRYCRC_MSG_BAD_LAYOUT;
-  int64_t prev = -1, first = -1;
-  for (int k = 0; k < 5; ++k) {
-    if (rel[k] == -1) continue;
-    if (rel[k] <= prev || rel[k] < (int32_t)h) return AMBRYCRC_MSG_BAD_LAYOUT;
-    if (first < 0) first = rel[k];
-    prev = rel[k];
-  }
-  if ((uint64_t)m->total > rem || (uint64_t)first > rem - (uint64_t)m->total) return AMBRYCRC_MSG_BAD_LAYOUT;
-  const uint64_t end = (uint64_t)first + (uint64_t)m->total;
-  uint64_t rend[5];
-  for (int k = 0; k < 5; ++k) {
-    rend[k] = end;
-    for (int j = k + 1; j < 5; ++j)
-      if (rel[j] != -1) {
-        rend[k] = (uint64_t)rel[j];
-        break;
-      }
-    if (rel[k] != -1 && rend[k] < (uint64_t)rel[k] + 8) return AMBRYCRC_MSG_BAD_LAYOUT;
-  }
-  uint32_t status = 0;
-  for (int k = 0; k < 5; ++k) {
-    if (rel[k] == -1) continue;
-    const uint8_t* q = p + rel[k];
-    const uint64_t span = rend[k] - (uint64_t)rel[k];
-    if ((uint64_t)ambrycrc_update(0, q, span - 8) != rd64(q + span - 8)) status |= kRecordBit[k];
+// Header and every record of the message at p (rem bytes available): status bits; *end the message
+// end relative to p, 0 when the header is refused.
+uint32_t verify(const uint8_t* p, uint64_t rem, ambrycrc::MsgHeader* H, uint64_t* end) {
+  *end = 0;
+  ambrycrc::MsgLayout L;
+  uint32_t status = decode(p, rem, H);
+  if (status == 0) status = ambrycrc::msg_layout(*H, rem, &L);
+  if (status) return status;
+  for (int k = 0; k < ambrycrc::kMsgSlots; ++k) {
+    if (L.rel[k] == -1) continue;
+    const uint8_t* q = p + L.rel[k];
+    const uint64_t span = L.rend[k] - (uint64_t)L.rel[k];
+    if ((uint64_t)ambrycrc_update(0, q, span - 8) != ld_be64(q + span - 8)) status |= kRecordBit[k];
     status |= record_check(k, q, span);
   }
-  m->end = end;
+  *end = L.end;
   return status;
 }
 
@@ -138,51 +72,49 @@ struct XPlan {
 // msgInfo.getLifeVersion() unchanged, as the device batch does); otherwise keep the stored one.
 uint32_t transform_plan(const uint8_t* region, uint64_t region_len, uint64_t off, bool have_life, int life_version,
                         int header_version, XPlan* x) {
-  Parsed m;
-  m.end = 0;
-  const uint32_t st = off <= region_len ? verify(region + off, region_len - off, &m) : (uint32_t)AMBRYCRC_MSG_BAD_LAYOUT;
+  ambrycrc::MsgHeader H;
+  uint64_t end = 0;
+  const uint32_t st = off <= region_len ? verify(region + off, region_len - off, &H, &end) : (uint32_t)AMBRYCRC_MSG_BAD_LAYOUT;
   if (st) return st;
   const uint8_t* p = region + off;
-  const int32_t enc = m.rel[0], bp = m.rel[1], upd = m.rel[2], um = m.rel[3], blob = m.rel[4];
+  const int32_t enc = H.rel[0], bp = H.rel[1], upd = H.rel[2], um = H.rel[3], blob = H.rel[4];
   if (upd != -1 || bp == -1 || um == -1 || blob == -1) return AMBRYCRC_MSG_NOT_PUT;  // "cannot be anything rather than put record"
   // the deserializers' field reads (deserializeBlobEncryptionKey / Properties / UserMetadata / Blob,
-  // MessageFormatRecord.java:1568-1833); verify's record checks already hold for them
-  const int64_t first = enc != -1 ? enc : bp;
-  const uint32_t bv = rd16(p + blob);
-  const uint32_t head = bv == 1 ? 10u : bv == 2 ? 12u : 13u;
+  // MessageFormatRecord.java:1568-1833; msg_header.h put_fields); verify's record checks already hold for them
+  const ambrycrc::PutFields f = ambrycrc::put_fields(p, H);
   // deserializeBlobProperties, re-serialized at VERSION_5 (record_fields.h; verify parsed it)
-  const uint32_t stored = (uint32_t)(um - bp - 2 - 8);
+  const uint32_t stored = (uint32_t)f.props_len;
   ambrycrc::PropsFields pf;
-  if (ambrycrc::props_parse<true>(p + bp + 2, stored, &pf) != 0) return AMBRYCRC_MSG_BAD_RECORD;
+  if (!f.ok || ambrycrc::props_parse<true>(p + bp + 2, stored, &pf) != 0) return AMBRYCRC_MSG_BAD_RECORD;
   if (!pf.ascii) return AMBRYCRC_MSG_NOT_ENCODABLE;
   x->fx = ambrycrc::props_fix_of(pf, stored);
   // A V3 message with a V3 blob record and properties already canonical VERSION_5 bytes re-serializes
   // at V3 to its own bytes but for the life version and the header CRC (the GPU fast path's rule,
   // region_proc.h transform_fast): one copy and the 32-byte header's CRC, instead of the layout,
   // copy and every record CRC again.
-  if (header_version == 3 && m.version == 3 && bv == 3 && x->fx.version == 0) {
+  if (header_version == 3 && H.version == 3 && f.blob_version == 3 && x->fx.version == 0) {
     x->fast = true;
-    x->len = m.end;
-    x->life = have_life && (uint32_t)(uint16_t)life_version != m.life ? (int)(uint16_t)life_version : -1;
+    x->len = end;
+    x->life = have_life && (uint16_t)life_version != (uint16_t)H.life ? (int)(uint16_t)life_version : -1;
     return 0;
   }
   ambrycrc_put_desc& d = x->d;
   memset(&d, 0, sizeof d);
   const bool keep_enc = enc != -1 && header_version >= 2;
   d.out_off = 0;
-  d.key_src = off + m.hsize;
-  d.key_len = (uint32_t)(first - m.hsize);
+  d.key_src = off + H.hs;
+  d.key_len = (uint32_t)(f.first - H.hs);
   d.enckey_src = keep_enc ? off + enc + 6 : 0;
-  d.enckey_len = keep_enc ? (int32_t)rd32(p + enc + 2) : -1;
+  d.enckey_len = keep_enc ? (int32_t)f.enc_len : -1;
   d.props_src = off + bp + 2;
   d.props_len = ambrycrc::props_v5_len(x->fx);
   d.usermeta_src = off + um + 6;
-  d.usermeta_len = rd32(p + um + 2);
-  d.blob_src = off + blob + head;
-  d.blob_len = rd64(p + blob + (bv == 1 ? 2 : bv == 2 ? 4 : 5));
-  d.life_version = (int16_t)(have_life ? life_version : (int)m.life);
-  d.blob_type = (int16_t)(bv == 1 ? 0u : rd16(p + blob + 2));
-  d.compressed = (uint8_t)(bv == 3 && p[blob + 4] == 1 ? 1 : 0);
+  d.usermeta_len = f.um_len;
+  d.blob_src = off + blob + f.head;
+  d.blob_len = f.size;
+  d.life_version = (int16_t)(have_life ? life_version : H.life);
+  d.blob_type = (int16_t)f.type;
+  d.compressed = (uint8_t)f.comp;
   d.header_version = (uint8_t)header_version;
   x->len = ambrycrc_put_layout(&d, nullptr);
   return x->len ? 0u : (uint32_t)AMBRYCRC_MSG_BAD_RECORD;
@@ -213,29 +145,15 @@ int transform_emit(const uint8_t* region, uint64_t off, const XPlan& x, uint8_t*
   return AMBRYCRC_OK;
 }
 
-// Hard delete: the header work of `verify` alone (version, verifyHeader, checkHeaderConstraints, the
-// message inside rem), then the user-metadata and blob spans (hard_delete.h).
+// Hard delete: the header's verdict and layout alone, then the user-metadata and blob spans (hard_delete.h).
 uint32_t hd_header(const uint8_t* p, uint64_t rem, int* version, ambrycrc::HdSpans* s) {
-  if (rem < 2) return AMBRYCRC_MSG_BAD_LAYOUT;
-  const int v = (int16_t)rd16(p);
-  const uint32_t h = v == 1 ? 34u : v == 2 ? 38u : v == 3 ? 40u : 0u;
-  if (h == 0) return AMBRYCRC_MSG_BAD_VERSION;
-  if (rem < h) return AMBRYCRC_MSG_BAD_LAYOUT;
-  if ((uint64_t)ambrycrc_update(0, p, h - 8) != rd64(p + h - 8)) return AMBRYCRC_MSG_HEADER_CRC;
-  int life = 0;
-  int64_t total;
-  int32_t rel[5];
-  if (v == 3) {
-    life = (int16_t)rd16(p + 2);
-    total = (int64_t)rd64(p + 4);
-    for (int k = 0; k < 5; ++k) rel[k] = (int32_t)rd32(p + 12 + 4 * k);
-  } else {
-    total = (int64_t)rd64(p + 2);
-    rel[0] = -1;
-    for (int k = v == 1 ? 1 : 0; k < 5; ++k) rel[k] = (int32_t)rd32(p + 10 + 4 * (k - (v == 1 ? 1 : 0)));
-  }
-  *version = v;
-  return ambrycrc::hd_header_spans(h, life, total, rel, rem, s);
+  ambrycrc::MsgHeader H;
+  ambrycrc::MsgLayout L;
+  uint32_t st = decode(p, rem, &H);
+  if (st == 0) st = ambrycrc::msg_layout(H, rem, &L);
+  if (st) return st;
+  *version = H.version;
+  return ambrycrc::hd_header_spans(H, L, s);
 }
 
 }  // namespace
@@ -267,13 +185,13 @@ int ambrycrc_hard_delete_message_cpu(uint8_t* region, uint64_t region_len, uint6
     const uint8_t* um = p + s.um_rel;
     const uint8_t* bl = p + s.blob_rel;
     st |= record_check(3, um, s.um_span);
-    if ((uint64_t)ambrycrc_update(0, um, s.um_span - 8) != rd64(um + s.um_span - 8)) st |= AMBRYCRC_MSG_USERMETA_CRC;
+    if ((uint64_t)ambrycrc_update(0, um, s.um_span - 8) != ld_be64(um + s.um_span - 8)) st |= AMBRYCRC_MSG_USERMETA_CRC;
     st |= record_check(4, bl, s.blob_span);
-    if ((uint64_t)ambrycrc_update(0, bl, s.blob_span - 8) != rd64(bl + s.blob_span - 8)) st |= AMBRYCRC_MSG_BLOB_CRC;
+    if ((uint64_t)ambrycrc_update(0, bl, s.blob_span - 8) != ld_be64(bl + s.blob_span - 8)) st |= AMBRYCRC_MSG_BLOB_CRC;
     if (st == 0) {
-      const int bv = (int)rd16(bl);
-      o = ambrycrc::hd_info(hv, s, rd32(um + 2), bv, bv == 1 ? 0 : (int)rd16(bl + 2),
-                            rd64(bl + (bv == 1 ? 2 : bv == 2 ? 4 : 5)));
+      const int bv = (int)ld_be16(bl);
+      o = ambrycrc::hd_info(hv, s, ld_be32(um + 2), bv, bv == 1 ? 0 : (int)ld_be16(bl + 2),
+                            ld_be64(bl + ambrycrc::blob_head(bv) - 8));
     }
   }
   *status = st;
@@ -298,9 +216,10 @@ int ambrycrc_hard_delete_message_cpu(uint8_t* region, uint64_t region_len, uint6
 int ambrycrc_verify_message_cpu(const uint8_t* region, uint64_t region_len, uint64_t off, uint32_t* status,
                                 uint64_t* msg_end) {
   if (!region || !status) return AMBRYCRC_EINVAL;
-  Parsed m;
-  *status = off <= region_len ? verify(region + off, region_len - off, &m) : (uint32_t)AMBRYCRC_MSG_BAD_LAYOUT;
-  if (msg_end) *msg_end = off <= region_len && m.end ? off + m.end : 0;
+  ambrycrc::MsgHeader H;
+  uint64_t end = 0;
+  *status = off <= region_len ? verify(region + off, region_len - off, &H, &end) : (uint32_t)AMBRYCRC_MSG_BAD_LAYOUT;
+  if (msg_end) *msg_end = end ? off + end : 0;
   return AMBRYCRC_OK;
 }
 
@@ -311,19 +230,20 @@ int ambrycrc_recover_messages_cpu(const uint8_t* region, uint64_t region_len, ui
                                   ambrycrc_recover_result* result) {
   if ((!region && region_len) || !msg_off || !result || start > region_len || max_m == 0 || max_m >= (1ull << 31))
     return AMBRYCRC_EINVAL;
-  const auto crc = [](const uint8_t* p, uint32_t n) { return ambrycrc_update(0, p, n); };
   ambrycrc_recover_result r;
   memset(&r, 0, sizeof r);
   uint64_t off = start, first_bad = max_m;
   uint32_t bad_status = 0;
   while (off < region_len && r.chained < max_m) {
     uint64_t next = 0;
-    r.end_status = ambrycrc::chain_header(region + off, region_len - off, crc, &next);
+    const uint8_t* p = region + off;
+    r.end_status = ambrycrc::msg_chain_accept(ambrycrc::HeaderBytes{p}, region_len - off, HostCrc{p}, &next);
     if (r.end_status) break;
     const size_t i = (size_t)r.chained++;
     msg_off[i] = off;
-    Parsed m;
-    uint32_t st = verify(region + off, region_len - off, &m);
+    ambrycrc::MsgHeader H;
+    uint64_t end = 0;
+    uint32_t st = verify(p, region_len - off, &H, &end);
     ambrycrc_message_info o;
     memset(&o, 0, sizeof o);
     if (st == 0) st = ambrycrc::message_info_fields(region + off, off, &o);
@@ -390,9 +310,9 @@ int ambrycrc_rekey_message_cpu(const uint8_t* region, uint64_t region_len, uint6
     *status = AMBRYCRC_MSG_BAD_DESC;
     return AMBRYCRC_OK;
   }
-  Parsed m;
-  m.end = 0;
-  *status = off <= region_len ? verify(region + off, region_len - off, &m) : (uint32_t)AMBRYCRC_MSG_BAD_LAYOUT;
+  ambrycrc::MsgHeader H;
+  uint64_t end = 0;
+  *status = off <= region_len ? verify(region + off, region_len - off, &H, &end) : (uint32_t)AMBRYCRC_MSG_BAD_LAYOUT;
   if (*status) return AMBRYCRC_OK;
   ambrycrc_put_desc d;
   ambrycrc::RekeyFix x;
@@ -436,17 +356,17 @@ int ambrycrc_send_message_cpu(const uint8_t* region, uint64_t region_len, uint64
   const bool whole_verify = flag == AMBRYCRC_SEND_ALL || flag == AMBRYCRC_SEND_BLOB;
   ambrycrc::SendHeader H;
   memset(&H, 0, sizeof H);
-  uint32_t hdr = AMBRYCRC_MSG_BAD_LAYOUT, hs = 0;
+  uint32_t hdr = AMBRYCRC_MSG_BAD_LAYOUT;
   if (in_region && !(has_size && size > rem)) {
-    hdr = ambrycrc::send_header_size(p, rem, &hs);
-    if (hdr == 0 && (uint64_t)ambrycrc_update(0, p, hs - 8) != rd64(p + hs - 8)) hdr = AMBRYCRC_MSG_HEADER_CRC;
-    if (hdr == 0) hdr = ambrycrc::send_header_fields(p, rem, hs, &H);
+    ambrycrc::MsgHeader D;
+    hdr = decode(p, rem, &D);
+    if (hdr == 0) hdr = ambrycrc::msg_layout(D, rem, &H);
   }
   // a record's CRC against its stored long
   auto crc_bad = [&](int k) {
     const uint8_t* q = p + H.rel[k];
     const uint64_t span = H.rend[k] - (uint64_t)H.rel[k];
-    return (uint64_t)ambrycrc_update(0, q, span - 8) != rd64(q + span - 8);
+    return (uint64_t)ambrycrc_update(0, q, span - 8) != ld_be64(q + span - 8);
   };
   const bool enc_bad = hdr == 0 && ambrycrc::send_reads_enckey(flag) && H.rel[0] != -1 && H.rel[2] == -1 && crc_bad(0);
   ambrycrc::SendPlan s;
@@ -456,8 +376,9 @@ int ambrycrc_send_message_cpu(const uint8_t* region, uint64_t region_len, uint64
   uint32_t vbits = 0;  // the verify's bits that belong in check
   if (hdr == 0) {
     if (whole_verify) {
-      Parsed m;
-      vbits = verify(p, rem, &m);
+      ambrycrc::MsgHeader D;
+      uint64_t end = 0;
+      vbits = verify(p, rem, &D, &end);
     } else {
       for (int k = 1; k <= 3; k += 2)
         if (s.dst[k] != ambrycrc::kSendNone && crc_bad(k)) vbits |= kRecordBit[k];

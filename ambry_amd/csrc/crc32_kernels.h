@@ -7,6 +7,7 @@
 
 #include "../../include/ambrycrc.h"
 #include "build_knobs.h"
+#include "msg_header.h"
 
 namespace ambrycrc {
 
@@ -187,9 +188,8 @@ inline size_t region_ws_bytes(const uint8_t* region, uint64_t len, uint64_t m) {
 }
 hipError_t launch_region_runs(const RegionArgs& a, int grid, hipStream_t s);
 
-// Message verify (message_kernels.hip): kMsgSlots CRC jobs per message, slot order
-// encryption key, blob properties, update, user metadata, blob.
-constexpr int kMsgSlots = 5;
+// Message verify (message_kernels.hip): kMsgSlots CRC jobs per message, in the header's slot order
+// (msg_header.h).
 
 struct MsgArgs {
   const uint8_t* region;

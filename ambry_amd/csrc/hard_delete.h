@@ -1,5 +1,5 @@
 // hard_delete.h -- what the device hard delete (hard_delete_kernels.hip) and the per-message CPU entry
-// (ambrycrc_hard_delete_message_cpu) share: the header's record spans, the recovery-info check and
+// (ambrycrc_hard_delete_message_cpu) share: the two record spans of a header, the recovery-info check and
 // the record prefixes HardDeleteMessageFormatInputStream writes
 // (ambry-messageformat/.../HardDeleteMessageFormatInputStream.java:58-124):
 //   UserMetadata_Format_V1   short 1, int size, zeros, CRC      (MessageFormatRecord.java:1619-1635)
@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/ambrycrc.h"
+#include "msg_header.h"
 #include "put_layout.h"
 
 namespace ambrycrc {
@@ -25,53 +26,22 @@ struct HdSpans {
   uint64_t um_span, blob_span;  // stored CRC included
 };
 
-// checkHeaderConstraints (MessageFormatRecord.java:985-1030) and the record spans, for a header of
-// h bytes whose CRC verified (the checks of msg_parse.h parse_message, in its order): rel[] =
-// encryption key, properties, update, user metadata, blob relative offsets (-1 absent), life the V3
-// life version (0 for V1/V2), rem the region bytes from the message start. AMBRYCRC_MSG_BAD_LAYOUT,
-// AMBRYCRC_MSG_NOT_PUT for an update message (BlobStoreHardDelete.java:129-131), or 0 with *s set.
-__host__ __device__ inline uint32_t hd_header_spans(uint32_t h, int life, int64_t total, const int32_t (&rel)[5],
-                                                    uint64_t rem, HdSpans* s) {
-  const bool is_put = rel[1] != -1 && rel[2] == -1 && rel[3] != -1 && rel[4] != -1;
-  const bool is_upd = rel[2] != -1 && rel[0] == -1 && rel[1] == -1 && rel[3] == -1 && rel[4] == -1;
-  if (life < 0 || total <= 0 || !(is_put || is_upd)) return AMBRYCRC_MSG_BAD_LAYOUT;
-  int64_t prev = -1, first = -1;
-  for (int k = 0; k < 5; ++k) {
-    if (rel[k] == -1) continue;
-    if (rel[k] <= prev || rel[k] < (int32_t)h) return AMBRYCRC_MSG_BAD_LAYOUT;
-    if (first < 0) first = rel[k];
-    prev = rel[k];
-  }
-  if ((uint64_t)total > rem || (uint64_t)first > rem - (uint64_t)total) return AMBRYCRC_MSG_BAD_LAYOUT;
-  const uint64_t end = (uint64_t)first + (uint64_t)total;
-  for (int k = 0; k < 5; ++k) {  // every record holds its CRC at least
-    if (rel[k] == -1) continue;
-    uint64_t rend = end;
-    for (int j = k + 1; j < 5; ++j)
-      if (rel[j] != -1) {
-        rend = (uint64_t)rel[j];
-        break;
-      }
-    if (rend < (uint64_t)rel[k] + 8) return AMBRYCRC_MSG_BAD_LAYOUT;
-  }
-  if (is_upd) return AMBRYCRC_MSG_NOT_PUT;
-  s->um_rel = (uint32_t)rel[3];
-  s->blob_rel = (uint32_t)rel[4];
-  s->um_span = (uint64_t)rel[4] - (uint64_t)rel[3];
-  s->blob_span = end - (uint64_t)rel[4];
-  return 0;
-}
-
-// Bytes of a blob record before its content (0: an unknown version).
-__host__ __device__ inline uint32_t hd_blob_head(int version) {
-  return version == 1 ? 10u : version == 2 ? 12u : version == 3 ? 13u : 0u;
+// The two spans of a header msg_layout accepted (msg_header.h), or AMBRYCRC_MSG_NOT_PUT for an update
+// message (BlobStoreHardDelete.java:129-131). From the two offsets and the message end, which for a PUT
+// are L.rend[3] and L.rend[4]: read from rend[] hd_parse_kernel needs 75 VGPRs for 69 and loses a wave.
+__host__ __device__ inline uint32_t hd_header_spans(const MsgHeader& H, const MsgLayout& L, HdSpans* s) {
+  s->um_rel = (uint32_t)H.rel[3];
+  s->blob_rel = (uint32_t)H.rel[4];
+  s->um_span = (uint64_t)H.rel[4] - (uint64_t)H.rel[3];  // a PUT: the blob record follows, then the message ends
+  s->blob_span = L.end - (uint64_t)H.rel[4];
+  return H.rel[2] != -1 ? (uint32_t)AMBRYCRC_MSG_NOT_PUT : 0u;  // (*s is then meaningless)
 }
 
 // Recovery info against the header's spans: valid versions and blob type, and sizes that put the two
 // records exactly on their spans -- an in-place writer never writes outside them (the reference
 // trusts its own token, BlobStoreHardDelete.java:160-165).
 __host__ __device__ inline bool hd_recovery_ok(const ambrycrc_hard_delete_info& r, const HdSpans& s) {
-  const uint32_t head = hd_blob_head(r.blob_version);
+  const uint32_t head = blob_head(r.blob_version);
   if (r.usermeta_version != 1 || head == 0 || r.blob_type < 0 || r.blob_type >= 2) return false;
   return (uint64_t)r.usermeta_size + 14 == s.um_span && r.blob_size <= s.blob_span &&
          r.blob_size + head + 8 == s.blob_span;

@@ -3,8 +3,8 @@
 // many stored PUT messages of a log region in HBM, in place.
 //
 // Pipeline (all on the caller's stream; ambrycrc_hd.cpp):
-//   hd_parse_kernel  one thread per message: header version, header CRC, header constraints (as
-//                    msg_parse_kernel, without the properties), update messages refused, then either
+//   hd_parse_kernel  one thread per message: the header's verdict and spans (msg_header.h, from the
+//                    header words of msg_parse.h), update messages refused, then either
 //                    the recovery info checked against the header's spans, or the user-metadata and
 //                    blob records' field checks and two CRC jobs (the records less their stored CRCs)
 //   plan + sweep     the batch CRC engine over the 2m jobs (crc32_kernels.hip; empty jobs cost nothing)
@@ -39,51 +39,15 @@ __global__ __launch_bounds__(256) void hd_parse_kernel(HdArgs a) {
     const uint64_t rem = in_region ? a.region_len - off : 0;
     const uint8_t* p = a.region + (in_region ? off : 0);
     const HeaderWords hw = load_header(p, rem);
-    uint32_t status = 0;
-    int v = 0;
+    uint32_t status;
     HdSpans s{0, 0, 0, 0};
-    do {  // the header work of parse_message (msg_parse.h), then the two spans (hard_delete.h)
-      if (!in_region || rem < 2) {
-        status = AMBRYCRC_MSG_BAD_LAYOUT;
-        break;
-      }
-      v = (int16_t)__builtin_bswap16((uint16_t)hw.w[0]);
-      const uint32_t h = v == 1 ? 34u : v == 2 ? 38u : v == 3 ? 40u : 0u;
-      if (h == 0) {
-        status = AMBRYCRC_MSG_BAD_VERSION;
-        break;
-      }
-      if (rem < h) {
-        status = AMBRYCRC_MSG_BAD_LAYOUT;
-        break;
-      }
-      const uint32_t st_hi = v == 3 ? be32_w0(hw, 8) : v == 2 ? be32_w2(hw, 7) : be32_w2(hw, 6);
-      const uint32_t st_lo = v == 3 ? be32_w0(hw, 9) : v == 2 ? be32_w2(hw, 8) : be32_w2(hw, 7);
-      if (st_hi != 0 || header_crc(hw, h - 8, tbl) != st_lo) {  // verifyHeader
-        status = AMBRYCRC_MSG_HEADER_CRC;
-        break;
-      }
-      int life = 0;
-      int64_t total;
-      int32_t rel[5];
-      if (v == 3) {
-        life = (int16_t)__builtin_bswap16((uint16_t)(hw.w[0] >> 16));
-        total = (int64_t)(((uint64_t)be32_w0(hw, 1) << 32) | be32_w0(hw, 2));
-#pragma unroll
-        for (int k = 0; k < 5; ++k) rel[k] = (int32_t)be32_w0(hw, 3 + k);
-      } else {
-        total = (int64_t)(((uint64_t)be32_w2(hw, 0) << 32) | be32_w2(hw, 1));
-        if (v == 1) {
-          rel[0] = -1;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) rel[k + 1] = (int32_t)be32_w2(hw, 2 + k);
-        } else {
-#pragma unroll
-          for (int k = 0; k < 5; ++k) rel[k] = (int32_t)be32_w2(hw, 2 + k);
-        }
-      }
-      status = hd_header_spans(h, life, total, rel, rem, &s);
-    } while (false);
+    // the header's verdict and record spans (msg_header.h), then the two spans (hard_delete.h)
+    MsgHeader H;
+    MsgLayout L;
+    status = in_region ? msg_decode(HeaderWordSrc{hw}, rem, HeaderWordCrc{hw, tbl}, &H) : (uint32_t)AMBRYCRC_MSG_BAD_LAYOUT;
+    if (status == 0) status = msg_layout(H, rem, &L);
+    if (status == 0) status = hd_header_spans(H, L, &s);
+    const int v = H.version;  // read only where the status is 0
     uint64_t jo[2] = {0, 0}, jl[2] = {0, 0};
     uint32_t ex[2] = {0, 0}, check = 0;
     ambrycrc_hard_delete_info o;
@@ -99,7 +63,7 @@ __global__ __launch_bounds__(256) void hd_parse_kernel(HdArgs a) {
         const uint8_t* um = p + s.um_rel;
         const uint8_t* bl = p + s.blob_rel;
         status = record_check(3, um, s.um_span) | record_check(4, bl, s.blob_span);
-        const uint64_t um_crc = be64(um + s.um_span - 8), bl_crc = be64(bl + s.blob_span - 8);
+        const uint64_t um_crc = ld_be64(um + s.um_span - 8), bl_crc = ld_be64(bl + s.blob_span - 8);
         if (um_crc >> 32) status |= AMBRYCRC_MSG_USERMETA_CRC;  // a CRC32 never has upper bits
         if (bl_crc >> 32) status |= AMBRYCRC_MSG_BLOB_CRC;
         jo[0] = off + s.um_rel;
@@ -110,9 +74,8 @@ __global__ __launch_bounds__(256) void hd_parse_kernel(HdArgs a) {
         ex[1] = (uint32_t)bl_crc;
         check = 1;
         if (status == 0) {  // the fields record_check just validated
-          const int bv = (int)be16(bl);
-          o = hd_info(v, s, be32(um + 2), bv, bv == 1 ? 0 : (int)be16(bl + 2),
-                      be64(bl + (bv == 1 ? 2 : bv == 2 ? 4 : 5)));
+          const int bv = (int)ld_be16(bl);
+          o = hd_info(v, s, ld_be32(um + 2), bv, bv == 1 ? 0 : (int)ld_be16(bl + 2), ld_be64(bl + blob_head(bv) - 8));
         }
       }
     }

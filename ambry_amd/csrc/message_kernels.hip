@@ -203,7 +203,7 @@ __global__ __launch_bounds__(256) void trailer_parse_kernel(TrailerArgs a) {
   } else {
     jl = len - 8;
     if (jl == 0 || jl > a.inline_max) {  // else the group phase reads it (SweepArgs::exp_fill)
-      const uint64_t stored = be64(a.base + a.off[i] + jl);
+      const uint64_t stored = ld_be64(a.base + a.off[i] + jl);
       ex = (uint32_t)stored;
       force = (stored >> 32) ? 1 : 0;
     }
@@ -279,64 +279,24 @@ __device__ __forceinline__ void transform_describe(const TransformArgs& a, uint6
   if (st == 0) {  // verified: the header and every record lie inside the region
     const uint64_t off = a.msg_off[i];
     const uint8_t* p = a.region + off;
-    const uint32_t v = be16(p);
-    const uint32_t hs = v == 1 ? 34u : v == 2 ? 38u : 40u;
-    int32_t rel[5];
-    int64_t total;
-    uint32_t life = 0;
-    if (v == 1) {
-      total = (int64_t)be64(p + 2);
-      rel[0] = -1;
-      for (int k = 0; k < 4; ++k) rel[k + 1] = (int32_t)be32(p + 10 + 4 * k);
-    } else if (v == 2) {
-      total = (int64_t)be64(p + 2);
-      for (int k = 0; k < 5; ++k) rel[k] = (int32_t)be32(p + 10 + 4 * k);
-    } else {
-      life = be16(p + 2);
-      total = (int64_t)be64(p + 4);
-      for (int k = 0; k < 5; ++k) rel[k] = (int32_t)be32(p + 12 + 4 * k);
-    }
-    const int32_t enc = rel[0], bp = rel[1], upd = rel[2], um = rel[3], blob = rel[4];
+    const MsgHeader H = msg_header_of(p);
+    const uint32_t hs = H.hs;
+    const int32_t enc = H.rel[0], bp = H.rel[1], upd = H.rel[2], um = H.rel[3], blob = H.rel[4];
     if (upd != -1 || bp == -1 || um == -1 || blob == -1) {
       st |= AMBRYCRC_MSG_NOT_PUT;
     } else {
-      const int64_t first = enc != -1 ? enc : bp;
-      const int64_t end = first + total;  // message end, relative
-      bool ok = first >= (int64_t)hs;
-      uint32_t enc_len = 0;
-      if (enc != -1) {  // BlobEncryptionKey_Format_V1: version, int size, key, CRC
-        enc_len = be32(p + enc + 2);
-        ok = ok && (int64_t)enc + 6 + enc_len + 8 == bp;
-      }
-      const int64_t props_len = (int64_t)um - bp - 2 - 8;  // BlobProperties_Format_V1: version, props, CRC
-      const uint32_t um_len = be32(p + um + 2);             // UserMetadata_Format_V1: version, int size, ..., CRC
-      ok = ok && props_len >= 0 && (int64_t)um + 6 + um_len + 8 == blob;
+      // the deserializers' field reads against the header's spans (msg_header.h put_fields)
+      const PutFields f = put_fields(p, H);
+      const int64_t first = f.first, end = f.end;  // message end, relative
+      const uint32_t head = f.head, type = f.type, comp = f.comp, bv = f.blob_version;
+      const uint64_t size = f.size;
+      bool ok = f.ok;
       // deserializeBlobProperties -> serializeBlobProperties at VERSION_5 (record_fields.h)
       PropsFields pf;
       if (pre) pf = *pre;  // the fused parse kernel parsed them already (from its LDS window)
-      else ok = ok && props_parse<true>(p + bp + 2, (uint64_t)props_len, &pf) == 0;
+      else ok = ok && props_parse<true>(p + bp + 2, (uint64_t)f.props_len, &pf) == 0;
       const bool encodable = !ok || pf.ascii;
-      const PropsFix fx = ok ? props_fix_of(pf, (uint32_t)props_len) : PropsFix{};
-      const uint32_t bv = be16(p + blob);  // Blob_Format_V1 / V2 / V3 (:1668-1833)
-      uint32_t head = 0, type = 0, comp = 0;
-      uint64_t size = 0;
-      if (bv == 1) {
-        size = be64(p + blob + 2);
-        head = 10;
-      } else if (bv == 2) {
-        type = be16(p + blob + 2);
-        size = be64(p + blob + 4);
-        head = 12;
-      } else if (bv == 3) {
-        type = be16(p + blob + 2);
-        comp = p[blob + 4] == 1 ? 1u : 0u;  // `readByte() == 1`
-        size = be64(p + blob + 5);
-        head = 13;
-      } else {
-        ok = false;
-      }
-      // BlobType has two values (DataBlob, MetadataBlob); sizes above Integer.MAX_VALUE throw
-      ok = ok && type < 2 && size <= 0x7FFFFFFFull && (int64_t)blob + head + (int64_t)size + 8 == end;
+      const PropsFix fx = ok ? props_fix_of(pf, (uint32_t)f.props_len) : PropsFix{};
       if (!ok) {
         st |= AMBRYCRC_MSG_BAD_RECORD;
       } else if (!encodable) {
@@ -346,15 +306,15 @@ __device__ __forceinline__ void transform_describe(const TransformArgs& a, uint6
         d.key_len = (uint32_t)(first - hs);
         const bool keep_enc = enc != -1 && a.header_version >= 2;
         d.enckey_src = keep_enc ? off + enc + 6 : 0;
-        d.enckey_len = keep_enc ? (int32_t)enc_len : -1;
+        d.enckey_len = keep_enc ? (int32_t)f.enc_len : -1;
         d.props_src = off + bp + 2;
         d.props_len = props_v5_len(fx);
         a.pfix[i] = fx;
         d.usermeta_src = off + um + 6;
-        d.usermeta_len = um_len;
+        d.usermeta_len = f.um_len;
         d.blob_src = off + blob + head;
         d.blob_len = size;
-        d.life_version = a.life ? a.life[i] : (int16_t)life;
+        d.life_version = a.life ? a.life[i] : (int16_t)H.life;
         d.blob_type = (int16_t)type;
         d.compressed = (uint8_t)comp;
         d.header_version = (uint8_t)a.header_version;
@@ -366,10 +326,10 @@ __device__ __forceinline__ void transform_describe(const TransformArgs& a, uint6
         } else if (a.in_crc) {
           // every record of the input verified: its CRC is the low word of its 8-B trailer
           uint32_t* ic = a.in_crc + 4 * i;
-          ic[0] = keep_enc ? be32(p + bp - 4) : 0u;
-          ic[1] = props_v5_crc(a.img, p + bp, fx, be32(p + um - 4));
-          ic[2] = be32(p + blob - 4);
-          uint32_t cblob = be32(p + end - 4);
+          ic[0] = keep_enc ? ld_be32(p + bp - 4) : 0u;
+          ic[1] = props_v5_crc(a.img, p + bp, fx, ld_be32(p + um - 4));
+          ic[2] = ld_be32(p + blob - 4);
+          uint32_t cblob = ld_be32(p + end - 4);
           if (bv != 3) {  // the V3 head (version 3, type, compressed, size) replaces a V1/V2 head
             // crc(B||C) = crc(A||C) ^ (crc(A) ^ crc(B)) * x^(8|C|)  (zlib's crc32_combine)
             uint8_t h3[13];
@@ -453,7 +413,7 @@ __global__ __launch_bounds__(256) void transform_finish_kernel(TransformArgs a) 
     return;
   }
   const uint8_t* __restrict__ src = a.region + d.key_src;
-  uint8_t* __restrict__ dst = a.out + d.out_off + (d.header_version == 1 ? 34u : d.header_version == 2 ? 38u : 40u);
+  uint8_t* __restrict__ dst = a.out + d.out_off + msg_header_size(d.header_version);
   const uint32_t n = d.key_len;
   if (n < 8) {
     uint8_t t[8];

@@ -1,34 +1,16 @@
-// msg_parse.h -- one stored message's header, record checks and CRC jobs, for the thread-per-
-// message kernels of the message verify and transform (message_kernels.hip) and the region-mode
-// message processors (region_kernels.hip region_fused_kernel / region_tail_kernel).
+// msg_parse.h -- one stored message's header registers, properties window and CRC jobs, for the
+// thread-per-message kernels of the message verify and transform (message_kernels.hip) and the
+// region-mode message processors (region_kernels.hip region_fused_kernel / region_tail_kernel). The
+// header rule itself is msg_header.h's; this file gives it the header as ten registers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/ambrycrc.h"
 #include "crc32_kernels.h"
-#include "record_fields.h"
+#include "msg_header.h"
 
 namespace ambrycrc {
-
-// Big-endian fields at arbitrary byte offsets: one unaligned global load each (gfx9 global
-// memory runs in unaligned access mode; the compiler emits global_load_dword[x2] for these
-// memcpys), where byte-wise reads cost a load per byte.
-__device__ __forceinline__ uint32_t be16(const uint8_t* p) {
-  uint16_t v;
-  __builtin_memcpy(&v, p, 2);
-  return __builtin_bswap16(v);
-}
-__device__ __forceinline__ uint32_t be32(const uint8_t* p) {
-  uint32_t v;
-  __builtin_memcpy(&v, p, 4);
-  return __builtin_bswap32(v);
-}
-__device__ __forceinline__ uint64_t be64(const uint8_t* p) {
-  uint64_t v;
-  __builtin_memcpy(&v, p, 8);
-  return __builtin_bswap64(v);
-}
 
 // The status bit of record slot k (encryption key, properties, update, user metadata, blob).
 static_assert(AMBRYCRC_MSG_ENCKEY_CRC == 2u && AMBRYCRC_MSG_PROPS_CRC == 4u && AMBRYCRC_MSG_UPDATE_CRC == 8u &&
@@ -88,41 +70,25 @@ __device__ __forceinline__ uint32_t header_crc(const HeaderWords& h, uint32_t n,
   return ~c;
 }
 
-// What each record's deserializer reads before its CRC (MessageFormatRecord.java), for a record
-// of `span` bytes at q (its stored CRC the last 8): the record version (an unknown one throws
-// UnknownFormatVersion, :147-239) and the size fields that decide where the stream looks for
-// the CRC. BlobEncryptionKey_Format_V1 (:1588-1600) and UserMetadata_Format_V1 (:1637-1649): an
-// int size, then that many bytes, then the CRC; Blob_Format_V1/V2/V3 (:1681-1833): blob type
-// ordinal < 2, a long size <= Integer.MAX_VALUE, then the content and the CRC. A size that
-// disagrees with the header's record span, or a bad type, is AMBRYCRC_MSG_BAD_RECORD (the
-// reference reads the CRC at a different place, or throws). BlobProperties_Format_V1 and
-// Update_Format_V1..V3: their fields, to the CRC (record_fields.h).
-__device__ __forceinline__ uint32_t record_check(int k, const uint8_t* q, uint64_t span) {
-  if (span < 10) return AMBRYCRC_MSG_BAD_RECORD;  // a version and a CRC at least
-  const uint32_t v = be16(q);
-  switch (k) {
-    case 0:    // encryption key
-    case 3: {  // user metadata
-      if (v != 1) return AMBRYCRC_MSG_BAD_VERSION;
-      if (span < 14) return AMBRYCRC_MSG_BAD_RECORD;
-      const int32_t n = (int32_t)be32(q + 2);
-      return n >= 0 && (uint64_t)n + 14 == span ? 0u : AMBRYCRC_MSG_BAD_RECORD;
-    }
-    case 1:  // properties (msg_parse_kernel parses them from its LDS window instead)
-      return props_record_check(q, span);
-    case 2:  // update
-      return update_record_check(q, span);
-    default: {  // blob
-      if (v < 1 || v > 3) return AMBRYCRC_MSG_BAD_VERSION;
-      const uint32_t head = v == 1 ? 10u : v == 2 ? 12u : 13u;
-      if (span < head + 8) return AMBRYCRC_MSG_BAD_RECORD;
-      const uint32_t type = v == 1 ? 0u : be16(q + 2);
-      const uint64_t size = be64(q + (v == 1 ? 2 : v == 2 ? 4 : 5));
-      return type < 2 && size <= 0x7FFFFFFFull && size + head + 8 == span ? 0u : AMBRYCRC_MSG_BAD_RECORD;
-    }
+// msg_header.h's field source over the header words: a field at byte 4k is a byte swap, one at 4k + 2 an
+// alignbyte of two words and a swap; crc(n) hashes the words with the slice tables t.
+struct HeaderWordSrc {
+  const HeaderWords& h;
+  __device__ __forceinline__ uint32_t u16(uint32_t at) const {
+    return __builtin_bswap16((uint16_t)(h.w[at >> 2] >> (8 * (at & 3))));
   }
-}
-
+  __device__ __forceinline__ uint32_t u32(uint32_t at) const { return at & 2 ? be32_w2(h, at >> 2) : be32_w0(h, at >> 2); }
+  // the stored header CRC, the long at [hs - 8, hs): a select among the three layouts' words
+  __device__ __forceinline__ void stored_crc(int v, uint32_t, uint32_t* hi, uint32_t* lo) const {
+    *hi = v == 3 ? u32(32) : v == 2 ? u32(30) : u32(26);
+    *lo = v == 3 ? u32(36) : v == 2 ? u32(34) : u32(30);
+  }
+};
+struct HeaderWordCrc {
+  const HeaderWords& h;
+  const uint32_t* __restrict__ t;
+  __device__ __forceinline__ uint32_t operator()(uint32_t n) const { return header_crc(h, n, t); }
+};
 
 // The first bytes of a record staged in this thread's LDS slot, the rest read from global memory:
 // the properties parse walks int-length strings, one dependent read per field, which from LDS
@@ -165,88 +131,20 @@ __device__ __forceinline__ void parse_message(uint64_t off, bool in_region, uint
                                               uint32_t* __restrict__ slot, uint64_t inline_max, MsgParse& r,
                                               PropsFields& pf, bool& pf_ok) {
   do {
-    if (!in_region || rem < 2) {
-      r.status = AMBRYCRC_MSG_BAD_LAYOUT;
-      break;
-    }
-    const int v = (int16_t)__builtin_bswap16((uint16_t)hw.w[0]);
-    const uint32_t h = v == 1 ? 34u : v == 2 ? 38u : v == 3 ? 40u : 0u;
-    if (h == 0) {
-      r.status = AMBRYCRC_MSG_BAD_VERSION;
-      break;
-    }
-    if (rem < h) {
-      r.status = AMBRYCRC_MSG_BAD_LAYOUT;
-      break;
-    }
-    // stored header CRC: bytes [h-8, h)
-    const uint32_t st_hi = v == 3 ? be32_w0(hw, 8) : v == 2 ? be32_w2(hw, 7) : be32_w2(hw, 6);
-    const uint32_t st_lo = v == 3 ? be32_w0(hw, 9) : v == 2 ? be32_w2(hw, 8) : be32_w2(hw, 7);
-    if (st_hi != 0 || header_crc(hw, h - 8, tbl) != st_lo) {  // verifyHeader: nothing else is read
-      r.status = AMBRYCRC_MSG_HEADER_CRC;
-      break;
-    }
-    int64_t total;
-    int32_t rel[kMsgSlots];
-    if (v == 3) {
-      if ((int16_t)__builtin_bswap16((uint16_t)(hw.w[0] >> 16)) < 0) {  // lifeVersion >= 0
-        r.status = AMBRYCRC_MSG_BAD_LAYOUT;
-        break;
-      }
-      total = (int64_t)(((uint64_t)be32_w0(hw, 1) << 32) | be32_w0(hw, 2));
-#pragma unroll
-      for (int k = 0; k < 5; ++k) rel[k] = (int32_t)be32_w0(hw, 3 + k);
-    } else {
-      total = (int64_t)(((uint64_t)be32_w2(hw, 0) << 32) | be32_w2(hw, 1));
-      if (v == 1) {
-        rel[0] = -1;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) rel[k + 1] = (int32_t)be32_w2(hw, 2 + k);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) rel[k] = (int32_t)be32_w2(hw, 2 + k);
-      }
-    }
-    // checkHeaderConstraints (MessageFormatRecord.java:985-1030), exact put / update shapes
-    const bool is_put = rel[1] != -1 && rel[2] == -1 && rel[3] != -1 && rel[4] != -1;
-    const bool is_upd = rel[2] != -1 && rel[0] == -1 && rel[1] == -1 && rel[3] == -1 && rel[4] == -1;
-    if (total <= 0 || !(is_put || is_upd)) {
-      r.status = AMBRYCRC_MSG_BAD_LAYOUT;
-      break;
-    }
-    int64_t prev = -1, first = -1;
-    bool ok = true;
-    for (int k = 0; k < kMsgSlots; ++k) {
-      if (rel[k] == -1) continue;
-      if (rel[k] <= prev || rel[k] < (int32_t)h) ok = false;
-      if (first < 0) first = rel[k];
-      prev = rel[k];
-    }
-    if (!ok || (uint64_t)total > rem || (uint64_t)first > rem - (uint64_t)total) {
-      r.status = AMBRYCRC_MSG_BAD_LAYOUT;
-      break;
-    }
-    r.end = (uint64_t)first + (uint64_t)total;
-    uint64_t rend[kMsgSlots];  // end of record k (its stored CRC's last byte + 1)
-    for (int k = 0; k < kMsgSlots; ++k) {
-      rend[k] = r.end;
-      for (int j = k + 1; j < kMsgSlots; ++j)
-        if (rel[j] != -1) {
-          rend[k] = (uint64_t)rel[j];
-          break;
-        }
-      if (rel[k] != -1 && rend[k] < (uint64_t)rel[k] + 8) ok = false;
-    }
-    if (!ok) {
-      r.status = AMBRYCRC_MSG_BAD_LAYOUT;
-      r.end = 0;
-      break;
-    }
+    // the header's verdict and record spans (msg_header.h): nothing past the header is read before them
+    MsgHeader H;
+    MsgLayout L;
+    r.status = in_region ? msg_decode(HeaderWordSrc{hw}, rem, HeaderWordCrc{hw, tbl}, &H) : (uint32_t)AMBRYCRC_MSG_BAD_LAYOUT;
+    if (r.status == 0) r.status = msg_layout(H, rem, &L);
+    if (r.status) break;
+    r.end = L.end;
+    const int32_t(&rel)[kMsgSlots] = H.rel;
+    const uint64_t(&rend)[kMsgSlots] = L.rend;  // end of record k (its stored CRC's last byte + 1)
     if (!WIN && rel[1] != -1) {  // properties parsed from memory
       const uint8_t* q = p + rel[1];
       const uint64_t span = rend[1] - (uint64_t)rel[1];
       uint32_t ps = AMBRYCRC_MSG_BAD_RECORD;
-      if (span >= 10) ps = be16(q) != 1 ? AMBRYCRC_MSG_BAD_VERSION : props_parse_b<DESC>(MemBytes{q + 2}, span - 10, &pf);
+      if (span >= 10) ps = ld_be16(q) != 1 ? AMBRYCRC_MSG_BAD_VERSION : props_parse_b<DESC>(MemBytes{q + 2}, span - 10, &pf);
       pf_ok = ps == 0;
       r.status |= ps;
     }
@@ -266,7 +164,7 @@ __device__ __forceinline__ void parse_message(uint64_t off, bool in_region, uint
       if (span >= 10) {
         const uint32_t ver = w >= 2 ? (uint32_t)reinterpret_cast<const uint8_t*>(slot)[0] << 8 |
                                           reinterpret_cast<const uint8_t*>(slot)[1]
-                                    : be16(q);
+                                    : ld_be16(q);
         ps = ver != 1 ? AMBRYCRC_MSG_BAD_VERSION
                       : props_parse_b<DESC>(WinBytes{reinterpret_cast<const uint8_t*>(slot) + 2, q + 2,
                                                      w >= 2 ? w - 2 : 0u},
@@ -284,7 +182,7 @@ __device__ __forceinline__ void parse_message(uint64_t off, bool in_region, uint
       // Records the group phase takes whole have their stored CRC read there, from the line
       // it is already streaming (SweepArgs::exp_fill); only the others cost a fetch here.
       if (r.jl[k] == 0 || r.jl[k] > inline_max) {
-        const uint64_t stored = be64(p + e - 8);
+        const uint64_t stored = ld_be64(p + e - 8);
         if (stored >> 32) r.status |= record_bit(k);  // a CRC32 never has upper bits: mismatch regardless
         r.ex[k] = (uint32_t)stored;
       }
@@ -296,24 +194,7 @@ __device__ __forceinline__ void parse_message(uint64_t off, bool in_region, uint
 // is unparseable or the message overruns `rem` -- what parse_message would read up to, from the
 // header words alone (no CRC check): the region-mode processors' wait target.
 __device__ __forceinline__ uint64_t header_end(const HeaderWords& hw, uint64_t rem) {
-  if (rem < 2) return 0;
-  const int v = (int16_t)__builtin_bswap16((uint16_t)hw.w[0]);
-  const uint32_t h = v == 1 ? 34u : v == 2 ? 38u : v == 3 ? 40u : 0u;
-  if (h == 0 || rem < h) return 0;
-  int64_t total;
-  int32_t first = -1;
-  if (v == 3) {
-    total = (int64_t)(((uint64_t)be32_w0(hw, 1) << 32) | be32_w0(hw, 2));
-    for (int k = 4; k >= 0; --k)
-      if ((int32_t)be32_w0(hw, 3 + k) != -1) first = (int32_t)be32_w0(hw, 3 + k);
-  } else {
-    total = (int64_t)(((uint64_t)be32_w2(hw, 0) << 32) | be32_w2(hw, 1));
-    const int nk = v == 1 ? 4 : 5;
-    for (int k = nk - 1; k >= 0; --k)
-      if ((int32_t)be32_w2(hw, 2 + k) != -1) first = (int32_t)be32_w2(hw, 2 + k);
-  }
-  if (total <= 0 || first < 0 || (uint64_t)total > rem || (uint64_t)first > rem - (uint64_t)total) return 0;
-  return (uint64_t)first + (uint64_t)total;
+  return msg_extent(HeaderWordSrc{hw}, rem);
 }
 
 }  // namespace ambrycrc

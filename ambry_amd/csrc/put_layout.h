@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "../../include/ambrycrc.h"
+#include "msg_header.h"
 
 namespace ambrycrc {
 
@@ -38,7 +39,7 @@ __host__ __device__ inline bool put_layout(const ambrycrc_put_desc& d, PutLayout
   const int v = d.header_version;
   if (v < 1 || v > 3) return false;
   if (d.enckey_len < -1 || (v == 1 && d.enckey_len >= 0)) return false;
-  L.hsize = v == 1 ? 34u : v == 2 ? 38u : 40u;
+  L.hsize = msg_header_size(v);
   L.enc_rec = d.enckey_len >= 0 ? 2ull + 4 + (uint64_t)d.enckey_len + 8 : 0;
   L.props_rec = 2ull + d.props_len + 8;
   L.um_rec = 2ull + 4 + d.usermeta_len + 8;

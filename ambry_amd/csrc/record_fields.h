@@ -8,6 +8,8 @@
 //     [v > 3] nullable int-string contentEncoding, filename,  [v > 4] reservedMetadataBlobId
 //   Update_Format_V1..V3 (MessageFormatRecord.java:1200-1480)
 //
+// and the big-endian readers (ld_be16 / 32 / 64) every parser of stored bytes uses.
+//
 // Every function reads only inside the span it is given: a field past it is the EOFException.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -223,10 +225,6 @@ __host__ __device__ inline void props_apply_fix(uint8_t* s, const PropsFix& x) {
   for (uint32_t i = 0; i < n; ++i) s[x.stored_len + i] = a[i];
 }
 
-// ---- the MessageInfo fields of recovery (BlobStoreRecovery.java:75-116), read from a message the
-// verify found clean (status 0: the header's constraints hold and every record parses, so each read
-// below lies inside its record).
-
 // Utils.addSecondsToEpochTime (Utils.java:1036-1041): Infinite_Time if either is, else
 // epoch + TimeUnit.SECONDS.toMillis(delta) -- toMillis saturates, the add wraps.
 __host__ __device__ inline int64_t add_seconds_to_epoch(int64_t epoch_ms, int64_t delta_s) {
@@ -234,60 +232,6 @@ __host__ __device__ inline int64_t add_seconds_to_epoch(int64_t epoch_ms, int64_
   const int64_t kMax = 0x7FFFFFFFFFFFFFFFll, kOver = kMax / 1000;
   const int64_t ms = delta_s > kOver ? kMax : delta_s < -kOver ? -kMax - 1 : delta_s * 1000;
   return (int64_t)((uint64_t)epoch_ms + (uint64_t)ms);
-}
-
-// Fills *o for the clean message at p, `off` bytes into its region. 0, or AMBRYCRC_MSG_BAD_INFO when
-// the operation time is below -1 (MessageInfo.java:172 throws); *o is then left zero.
-__host__ __device__ inline uint32_t message_info_fields(const uint8_t* p, uint64_t off, ambrycrc_message_info* o) {
-  __builtin_memset(o, 0, sizeof *o);
-  const uint32_t v = ld_be16(p);
-  const uint32_t h = v == 1 ? 34u : v == 2 ? 38u : 40u;
-  const uint8_t* r = p + (v == 3 ? 12 : 10);  // the relative offsets: V1 has no encryption-key slot
-  const int32_t enc = v == 1 ? -1 : (int32_t)ld_be32(r);
-  r += v == 1 ? 0 : 4;
-  const int32_t props = (int32_t)ld_be32(r), upd = (int32_t)ld_be32(r + 4);
-  const int32_t first = enc != -1 ? enc : props != -1 ? props : upd;
-  int64_t op_time, expires = -1;
-  int32_t account = -1, container = -1;
-  uint32_t flags = 0;
-  if (props != -1) {  // BlobProperties_Format_V1: record version, then the SerDe bytes
-    const uint8_t* s = p + props + 2;
-    const uint32_t sv = ld_be16(s);
-    const int64_t ttl = (int64_t)ld_be64(s + 2);
-    op_time = (int64_t)ld_be64(s + 11);
-    if (sv > 1) {  // the two shorts follow the three int-strings
-      uint64_t pos = kSerdeFixed;
-      for (int k = 0; k < 3; ++k) pos += 4 + (uint64_t)ld_be32(s + pos);
-      account = (int16_t)ld_be16(s + pos);
-      container = (int16_t)ld_be16(s + pos + 2);
-    }
-    expires = add_seconds_to_epoch(op_time, ttl);
-  } else {  // Update_Format_V1 (a delete, no fields: MessageFormatRecord.java:1242), V2 (a delete), V3
-    const uint8_t* q = p + upd;
-    const uint32_t uv = ld_be16(q);
-    op_time = -1;
-    uint32_t type = 0;
-    if (uv >= 2) {
-      account = (int16_t)ld_be16(q + 2);
-      container = (int16_t)ld_be16(q + 4);
-      op_time = (int64_t)ld_be64(q + 6);
-      if (uv == 3) type = ld_be16(q + 14);
-    }
-    flags = 1u << type;
-  }
-  if (op_time < -1) return AMBRYCRC_MSG_BAD_INFO;
-  o->msg_off = off;
-  o->size = (uint64_t)first + ld_be64(p + (v == 3 ? 4 : 2));
-  o->expires_at_ms = expires;
-  o->operation_time_ms = op_time;
-  o->key_rel = h;
-  o->key_len = (uint32_t)first - h;
-  o->account_id = (int16_t)account;
-  o->container_id = (int16_t)container;
-  o->life_version = (int16_t)(v == 3 ? ld_be16(p + 2) : 0u);
-  o->flags = (uint8_t)flags;
-  o->header_version = (uint8_t)v;
-  return 0;
 }
 
 }  // namespace ambrycrc

@@ -1,14 +1,13 @@
 // recover.h -- the device message chain and the MessageInfo extraction of a log region
-// (ambrycrc_chain_messages_dev, ambrycrc_recover_messages_dev / _cpu): the header
-// acceptance test as the CPU entry runs it (recover_kernels.hip restates it over msg_parse.h's header
-// words, one memory round trip a header), the scan geometry the tests build their lattices from, and
-// the kernels' arguments (recover_kernels.hip, ambrycrc_recover.cpp).
+// (ambrycrc_chain_messages_dev, ambrycrc_recover_messages_dev / _cpu): the scan geometry the
+// tests build their lattices from, the MessageInfo fields of a clean message, and the kernels' arguments
+// (recover_kernels.hip, ambrycrc_recover.cpp). The chain's acceptance test is msg_header.h msg_chain_accept.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/ambrycrc.h"
-#include "record_fields.h"
+#include "msg_header.h"
 
 namespace ambrycrc {
 
@@ -34,25 +33,58 @@ inline uint32_t chain_rounds(uint64_t max_m) {
   return r + 1;
 }
 
-// ambrycrc_chain_messages_host's acceptance test for the header at p with rem bytes to the region's
-// end, in the reference's order (BlobStoreRecovery.java:51-71): 0 and *next = first record offset +
-// message size, or why the walk stops here. crc(p, n): CRC-32 of n bytes at p.
-template <class Crc>
-__host__ __device__ inline uint32_t chain_header(const uint8_t* p, uint64_t rem, Crc crc, uint64_t* next) {
-  if (rem < 2) return AMBRYCRC_MSG_BAD_LAYOUT;
-  const int32_t v = (int16_t)ld_be16(p);
-  const uint32_t h = v == 1 ? 34u : v == 2 ? 38u : v == 3 ? 40u : 0u;
-  if (h == 0) return AMBRYCRC_MSG_BAD_VERSION;
-  if (rem < h) return AMBRYCRC_MSG_BAD_LAYOUT;
-  if (ld_be32(p + h - 8) != 0 || ld_be32(p + h - 4) != crc(p, h - 8)) return AMBRYCRC_MSG_HEADER_CRC;
-  const int64_t total = (int64_t)ld_be64(p + (v == 3 ? 4 : 2));
-  const uint8_t* r = p + (v == 3 ? 12 : 10);
-  int64_t first = -1;
-  for (int k = (v == 1 ? 4 : 5) - 1; k >= 0; --k)
-    if ((int32_t)ld_be32(r + 4 * k) != -1) first = (int32_t)ld_be32(r + 4 * k);
-  if (total <= 0 || first < (int64_t)h || (uint64_t)total > rem || (uint64_t)first > rem - (uint64_t)total)
-    return AMBRYCRC_MSG_BAD_LAYOUT;
-  *next = (uint64_t)first + (uint64_t)total;
+// ---- the MessageInfo fields of recovery (BlobStoreRecovery.java:75-116), read from a message the
+// verify found clean (status 0: the header's constraints hold and every record parses, so each read
+// below lies inside its record).
+
+// Fills *o for the clean message at p, `off` bytes into its region. 0, or AMBRYCRC_MSG_BAD_INFO when
+// the operation time is below -1 (MessageInfo.java:172 throws); *o is then left zero.
+__host__ __device__ inline uint32_t message_info_fields(const uint8_t* p, uint64_t off, ambrycrc_message_info* o) {
+  __builtin_memset(o, 0, sizeof *o);
+  const MsgHeader H = msg_header_of(p);
+  const uint32_t v = (uint32_t)H.version, h = H.hs;
+  const int32_t enc = H.rel[0], props = H.rel[1], upd = H.rel[2];
+  const int32_t first = enc != -1 ? enc : props != -1 ? props : upd;
+  int64_t op_time, expires = -1;
+  int32_t account = -1, container = -1;
+  uint32_t flags = 0;
+  if (props != -1) {  // BlobProperties_Format_V1: record version, then the SerDe bytes
+    const uint8_t* s = p + props + 2;
+    const uint32_t sv = ld_be16(s);
+    const int64_t ttl = (int64_t)ld_be64(s + 2);
+    op_time = (int64_t)ld_be64(s + 11);
+    if (sv > 1) {  // the two shorts follow the three int-strings
+      uint64_t pos = kSerdeFixed;
+      for (int k = 0; k < 3; ++k) pos += 4 + (uint64_t)ld_be32(s + pos);
+      account = (int16_t)ld_be16(s + pos);
+      container = (int16_t)ld_be16(s + pos + 2);
+    }
+    expires = add_seconds_to_epoch(op_time, ttl);
+  } else {  // Update_Format_V1 (a delete, no fields: MessageFormatRecord.java:1242), V2 (a delete), V3
+    const uint8_t* q = p + upd;
+    const uint32_t uv = ld_be16(q);
+    op_time = -1;
+    uint32_t type = 0;
+    if (uv >= 2) {
+      account = (int16_t)ld_be16(q + 2);
+      container = (int16_t)ld_be16(q + 4);
+      op_time = (int64_t)ld_be64(q + 6);
+      if (uv == 3) type = ld_be16(q + 14);
+    }
+    flags = 1u << type;
+  }
+  if (op_time < -1) return AMBRYCRC_MSG_BAD_INFO;
+  o->msg_off = off;
+  o->size = (uint64_t)first + (uint64_t)H.total;
+  o->expires_at_ms = expires;
+  o->operation_time_ms = op_time;
+  o->key_rel = h;
+  o->key_len = (uint32_t)first - h;
+  o->account_id = (int16_t)account;
+  o->container_id = (int16_t)container;
+  o->life_version = (int16_t)H.life;
+  o->flags = (uint8_t)flags;
+  o->header_version = (uint8_t)v;
   return 0;
 }
 

@@ -6,7 +6,7 @@
 // stream, no launch waiting on another workgroup:
 //   chain_scan          the region streamed once in 16-B nontemporal loads; every byte position tested
 //                       for a big-endian short in 1..3 (SWAR), each candidate validated with the chain's
-//                       acceptance test (recover.h chain_header); per kScanBlock bytes the node count
+//                       acceptance test (msg_header.h msg_chain_accept); per kScanBlock bytes the node count
 //                       and the in-block offsets of the first kStageMax nodes
 //   chain_tile_sums     the counts summed per tile of kSumTile blocks
 //   chain_prefix        one workgroup: exclusive prefix of the tile sums, the node total
@@ -37,9 +37,12 @@ namespace {
 
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 
-// recover.h's chain_header on the device: the header's 40 bytes in one round trip (msg_parse.h
-// load_header), every field and the CRC from those registers, as msg_parse_kernel hashes a header. t: the
-// LDS tables of stage_slice_tables. The same verdicts in the same order; the tests hold the two together.
+// The chain's acceptance test (msg_header.h msg_chain_accept) on the device: the header's 40 bytes in one
+// round trip (msg_parse.h load_header), every field and the CRC from those registers, as msg_parse_kernel
+// hashes a header. t: the LDS tables of stage_slice_tables. Written out here, not through msg_chain_accept:
+// the walk needs the first present offset alone, so V1's four offsets are read where V2 keeps its first four,
+// without the shift into the five slots -- through the shared decoder chain_rescan_kernel takes 7 more
+// SGPRs and loses a wave of occupancy. The header lattice tests hold it to the shared rule.
 struct LdsCrc {
   const uint32_t* t;
 };
@@ -48,7 +51,7 @@ __device__ __forceinline__ uint32_t chain_header(const uint8_t* p, uint64_t rem,
   if (rem < 2) return AMBRYCRC_MSG_BAD_LAYOUT;
   const HeaderWords hw = load_header(p, rem);
   const int v = (int16_t)__builtin_bswap16((uint16_t)hw.w[0]);
-  const uint32_t h = v == 1 ? 34u : v == 2 ? 38u : v == 3 ? 40u : 0u;
+  const uint32_t h = msg_header_size(v);
   if (h == 0) return AMBRYCRC_MSG_BAD_VERSION;
   if (rem < h) return AMBRYCRC_MSG_BAD_LAYOUT;
   const uint32_t st_hi = v == 3 ? be32_w0(hw, 8) : v == 2 ? be32_w2(hw, 7) : be32_w2(hw, 6);
@@ -59,17 +62,17 @@ __device__ __forceinline__ uint32_t chain_header(const uint8_t* p, uint64_t rem,
   if (v == 3) {
     total = (int64_t)(((uint64_t)be32_w0(hw, 1) << 32) | be32_w0(hw, 2));
 #pragma unroll
-    for (int k = 0; k < 5; ++k) rel[k] = (int32_t)be32_w0(hw, 3 + k);
+    for (int k = 0; k < kMsgSlots; ++k) rel[k] = (int32_t)be32_w0(hw, 3 + k);
   } else {
     total = (int64_t)(((uint64_t)be32_w2(hw, 0) << 32) | be32_w2(hw, 1));
     rel[4] = -1;  // V1 has four slots
 #pragma unroll
-    for (int k = 0; k < 5; ++k)
+    for (int k = 0; k < kMsgSlots; ++k)
       if (k < (v == 1 ? 4 : 5)) rel[k] = (int32_t)be32_w2(hw, 2 + k);
   }
   int64_t first = -1;
 #pragma unroll
-  for (int k = 4; k >= 0; --k)
+  for (int k = kMsgSlots - 1; k >= 0; --k)
     if (rel[k] != -1) first = rel[k];
   if (total <= 0 || first < (int64_t)h || (uint64_t)total > rem || (uint64_t)first > rem - (uint64_t)total)
     return AMBRYCRC_MSG_BAD_LAYOUT;

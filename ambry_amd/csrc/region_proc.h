@@ -350,13 +350,13 @@ __device__ __forceinline__ FastPre transform_fast_pre(const FusedArgs& f, const 
   if (off > a.region_len || a.region_len - off < end || end < 40) return r;
   const uint8_t* p = a.region + off;
   HeaderWords hw = load_header(p, 40);
-  if (be16(p) != 3) return r;
-  int32_t rel[kMsgSlots];
-#pragma unroll
-  for (int k = 0; k < kMsgSlots; ++k) rel[k] = (int32_t)be32_w0(hw, 3 + k);
+  if (ld_be16(p) != 3) return r;
+  MsgHeader H;
+  msg_fields(HeaderWordSrc{hw}, 3, &H);
+  const int32_t(&rel)[kMsgSlots] = H.rel;
   bool ok = rel[2] == -1 && rel[1] >= 0 && rel[3] >= 0 && rel[4] >= 0 && (int64_t)rel[3] >= (int64_t)rel[1] + 10 &&
             (uint64_t)rel[3] <= end && (uint64_t)rel[4] + 2 <= end;
-  if (ok) ok = be16(p + rel[4]) == 3;
+  if (ok) ok = ld_be16(p + rel[4]) == 3;
   if (ok) {  // properties already canonical VERSION_5 bytes, every string ASCII (record_fields.h)
     const uint32_t stored = (uint32_t)(rel[3] - rel[1] - 10);
     PropsFields pf;

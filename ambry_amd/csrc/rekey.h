@@ -14,8 +14,8 @@
 #include <stdint.h>
 
 #include "../../include/ambrycrc.h"
+#include "msg_header.h"
 #include "put_layout.h"
-#include "record_fields.h"
 
 namespace ambrycrc {
 
@@ -76,55 +76,15 @@ __host__ __device__ inline uint32_t rekey_plan(const uint8_t* region, uint64_t o
                                                bool have_life, int life_version, int header_version,
                                                ambrycrc_put_desc* d, RekeyFix* x) {
   const uint8_t* p = region + off;
-  const uint32_t v = ld_be16(p);
-  const uint32_t hs = v == 1 ? 34u : v == 2 ? 38u : 40u;
-  int32_t rel[5];
-  int64_t total;
-  uint32_t life = 0;
-  if (v == 3) {
-    life = ld_be16(p + 2);
-    total = (int64_t)ld_be64(p + 4);
-    for (int k = 0; k < 5; ++k) rel[k] = (int32_t)ld_be32(p + 12 + 4 * k);
-  } else {
-    total = (int64_t)ld_be64(p + 2);
-    rel[0] = -1;
-    for (int k = v == 1 ? 1 : 0; k < 5; ++k) rel[k] = (int32_t)ld_be32(p + 10 + 4 * (k - (v == 1 ? 1 : 0)));
-  }
-  const int32_t enc = rel[0], bp = rel[1], upd = rel[2], um = rel[3], blob = rel[4];
+  const MsgHeader H = msg_header_of(p);
+  const int32_t enc = H.rel[0], bp = H.rel[1], upd = H.rel[2], um = H.rel[3], blob = H.rel[4];
   if (upd != -1 || bp == -1 || um == -1 || blob == -1) return AMBRYCRC_MSG_NOT_PUT;  // "Only 'put' records are valid"
-  // the deserializers' field reads, as the transform's (message_kernels.hip transform_describe)
-  const int64_t first = enc != -1 ? enc : bp;
-  const int64_t end = first + total;
-  bool ok = first >= (int64_t)hs;
-  uint32_t enc_len = 0;
-  if (enc != -1) {
-    enc_len = ld_be32(p + enc + 2);
-    ok = ok && (int64_t)enc + 6 + enc_len + 8 == bp;
-  }
-  const int64_t props_len = (int64_t)um - bp - 2 - 8;
-  const uint32_t um_len = ld_be32(p + um + 2);
-  ok = ok && props_len >= 0 && (int64_t)um + 6 + um_len + 8 == blob;
+  // the deserializers' field reads against the header's spans (msg_header.h put_fields)
+  const PutFields f = put_fields(p, H);
+  const int64_t props_len = f.props_len;
+  const uint32_t head = f.head, type = f.type;
   PropsFields pf;
-  ok = ok && props_parse<true>(p + bp + 2, (uint64_t)props_len, &pf) == 0;
-  const uint32_t bv = ld_be16(p + blob);
-  uint32_t head = 0, type = 0, comp = 0;
-  uint64_t size = 0;
-  if (bv == 1) {
-    size = ld_be64(p + blob + 2);
-    head = 10;
-  } else if (bv == 2) {
-    type = ld_be16(p + blob + 2);
-    size = ld_be64(p + blob + 4);
-    head = 12;
-  } else if (bv == 3) {
-    type = ld_be16(p + blob + 2);
-    comp = p[blob + 4] == 1 ? 1u : 0u;
-    size = ld_be64(p + blob + 5);
-    head = 13;
-  } else {
-    ok = false;
-  }
-  ok = ok && type < 2 && size <= 0x7FFFFFFFull && (int64_t)blob + head + (int64_t)size + 8 == end;
+  const bool ok = f.ok && props_parse<true>(p + bp + 2, (uint64_t)props_len, &pf) == 0;
   if (!ok) return AMBRYCRC_MSG_BAD_RECORD;
   if (!pf.ascii) return AMBRYCRC_MSG_NOT_ENCODABLE;
   const bool repl = r.content_src != kRekeyKeep;
@@ -144,16 +104,16 @@ __host__ __device__ inline uint32_t rekey_plan(const uint8_t* region, uint64_t o
   d->key_src = r.key_src;
   d->key_len = r.key_len;
   d->enckey_src = keep_enc ? off + enc + 6 : 0;
-  d->enckey_len = keep_enc ? (int32_t)enc_len : -1;
+  d->enckey_len = keep_enc ? (int32_t)f.enc_len : -1;
   d->props_src = off + bp + 2;
   d->props_len = rekey_props_len(*x);
   d->usermeta_src = off + um + 6;
-  d->usermeta_len = um_len;
+  d->usermeta_len = f.um_len;
   d->blob_src = repl ? r.content_src : off + blob + head;
-  d->blob_len = repl ? r.content_len : size;
-  d->life_version = (int16_t)(have_life ? life_version : (int)life);
+  d->blob_len = repl ? r.content_len : f.size;
+  d->life_version = (int16_t)(have_life ? life_version : H.life);
   d->blob_type = (int16_t)type;
-  d->compressed = (uint8_t)comp;
+  d->compressed = (uint8_t)f.comp;
   d->header_version = (uint8_t)header_version;
   PutLayout L;
   if (!put_layout(*d, L)) {  // a relative offset past a Java int

@@ -49,9 +49,9 @@ __global__ __launch_bounds__(256) void send_plan_kernel(SendArgs a) {
       hdr = a.vstatus[i];
       if (hdr == 0) hdr = AMBRYCRC_MSG_BAD_LAYOUT;
     } else {
-      uint32_t hs = 0;
-      hdr = send_header_size(p, rem, &hs);
-      if (hdr == 0) hdr = send_header_fields(p, rem, hs, &H);
+      MsgHeader D;  // (its CRC verified by the parse)
+      hdr = msg_decode(HeaderBytes{p}, rem, NoCrc{}, &D);
+      if (hdr == 0) hdr = msg_layout(D, rem, &H);
     }
     bool enc_bad = false;
     if (a.enc_crc && hdr == 0 && H.rel[0] != -1)  // the stored long against the CRC of [rel, rend - 8)
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void send_plan_kernel(SendArgs a) {
     a.status[i] = s.status;
     a.len[i] = o.send_len;
 #pragma unroll
-    for (int k = 0; k < kSendSlots; ++k) {
+    for (int k = 0; k < kMsgSlots; ++k) {
       const uint64_t j = (uint64_t)k * m + i;
       const uint64_t d = s.status ? kSendNone : s.dst[k];
       if (d == kSendNone) {  // not read: an empty job, whose CRC (0) equals its expected value
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void send_jobs_kernel(SendArgs a) {
     }
     a.info[i].out_off = at;
 #pragma unroll
-    for (int k = 0; k < kSendSlots; ++k) {
+    for (int k = 0; k < kMsgSlots; ++k) {
       const uint64_t j = (uint64_t)k * m + i;
       const uint64_t c = a.copy_off[j];
       if (c != kCopySkip) a.copy_off[j] = at != kSendNowhere ? at + c : kCopySkip;
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void send_finish_kernel(SendArgs a) {
     // the trailers of the records the sweep copied (a job ends where its stored CRC starts)
     uint64_t lowest = kCopySkip;
 #pragma unroll
-    for (int k = 0; k < kSendSlots; ++k) {
+    for (int k = 0; k < kMsgSlots; ++k) {
       const uint64_t j = (uint64_t)k * m + i;
       const uint64_t c = a.copy_off[j];
       if (c == kCopySkip) continue;

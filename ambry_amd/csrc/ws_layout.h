@@ -239,7 +239,7 @@ inline IngestOwn ingest_own(Carver& c, size_t m, IngestArgs& a) {
 inline size_t ingest_own_bytes(size_t m) { return measure(ingest_own, m); }
 
 // ------------------------------------------------------------ send
-// Span lengths, message ends, the kSendSlots copy destinations a message, the plain-copy jobs (src, dst,
+// Span lengths, message ends, the kMsgSlots copy destinations a message, the plain-copy jobs (src, dst,
 // len, cost); then the verify's status, the encryption-key CRCs and the two scans' per-entry outputs.
 struct SendOwn {
   uint64_t* msg_end;                                   // a.msg_end, a.vstatus, a.enc_crc, writable
@@ -248,7 +248,7 @@ struct SendOwn {
 inline SendOwn send_own(Carver& c, size_t m, SendArgs& a) {
   SendOwn w;
   c.take_each(m, a.len, w.msg_end);
-  a.copy_off = c.take<uint64_t>((size_t)kSendSlots * m);
+  a.copy_off = c.take<uint64_t>((size_t)kMsgSlots * m);
   c.take_each(m, a.g_src, a.g_dst, a.g_len, a.g_cost);
   c.take_each(m, w.vstatus, w.enc_crc, w.scan_out, w.gscan_out);
   a.msg_end = w.msg_end;
