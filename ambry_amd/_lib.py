@@ -103,6 +103,13 @@ _SIGNATURES = [
     ("ambrycrc_send_message_cpu", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p,
       ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
+    ("ambrycrc_receive_workspace_size", ctypes.c_size_t, [ctypes.c_size_t]),
+    ("ambrycrc_receive_blobs_dev", ctypes.c_int,
+     [_u8p, ctypes.c_uint64, _u8p, _u8p, ctypes.c_size_t, ctypes.c_int, _u8p, _u8p, _u8p, ctypes.c_uint64, _u8p, _u8p,
+      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    ("ambrycrc_receive_blob_cpu", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+      ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
     ("ambrycrc_chain_workspace_bytes", ctypes.c_size_t, [ctypes.c_uint64, ctypes.c_size_t]),
     ("ambrycrc_chain_messages_dev", ctypes.c_int,
      [_u8p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t, _u8p, _u8p, ctypes.c_void_p, ctypes.c_size_t,

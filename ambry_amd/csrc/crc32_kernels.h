@@ -448,6 +448,40 @@ hipError_t launch_send_plan(const SendArgs& a, int num_cu, hipStream_t s);
 hipError_t launch_send_jobs(const SendArgs& a, int num_cu, hipStream_t s);
 hipError_t launch_send_finish(const SendArgs& a, int num_cu, hipStream_t s);
 
+// GET receive (recv_kernels.hip, ambrycrc_recv.cpp; the per-payload rules: recv.h): under ALL the verify's
+// parse, then one thread per payload decides what is refused and cuts the blob record into its CRC jobs,
+// the slices are placed (packed by a scan, or where the caller says), one copy-through CRC pass hashes
+// every job and writes the slices, and one thread per payload combines the pieces' CRCs and compares.
+struct RecvArgs {
+  const uint8_t* body;
+  uint64_t body_len;
+  const uint64_t* pay_off;     // [m]
+  const uint64_t* pay_size;    // [m] or null: each payload runs to the body's end
+  uint64_t m;
+  int flag;                    // AMBRYCRC_SEND_BLOB or AMBRYCRC_SEND_ALL
+  const uint64_t* range;       // [2m] or null: lo, hi
+  const uint64_t* dst_off;     // [m] or null: packed (start)
+  uint8_t* out;
+  uint64_t out_cap;
+  ::ambrycrc_recv_info* info;  // [m]
+  uint32_t* status;            // [m]
+  // ALL only: the verify's parse (MsgArgs) -- its status and message ends (0: the header did not parse)
+  const uint32_t* vstatus;     // [m]
+  const uint64_t* msg_end;     // [m]
+  // the CRC jobs, recv_slots(flag) a payload, slot-major, offsets from body; copy_off: the slice's place in
+  // out (slot kRecvSlice of a placed payload), kCopySkip everywhere else
+  uint64_t* job_off;
+  uint64_t* job_len;
+  uint64_t* copy_off;
+  const uint32_t* crc;         // the jobs' CRCs
+  uint64_t* len;               // [m] slice lengths, the placement scan's input
+  const uint64_t* start;       // [m + 1] their exclusive scan
+  const uint32_t* img;
+};
+hipError_t launch_recv_plan(const RecvArgs& a, int num_cu, hipStream_t s);
+hipError_t launch_recv_place(const RecvArgs& a, int num_cu, hipStream_t s);
+hipError_t launch_recv_finish(const RecvArgs& a, int num_cu, hipStream_t s);
+
 // ---- copy-mode serialization of small messages by streaming the output (round 6)
 // put_stream_kernel: a wave per message writes the whole message -- header and record heads computed,
 // fields and blob gathered from their sources, trailers zero -- in 16-B output pieces (four 1 KiB wave

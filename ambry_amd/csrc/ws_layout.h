@@ -22,6 +22,7 @@
 #include "put_request.h"
 #include "record_fields.h"
 #include "recover.h"
+#include "recv.h"
 #include "rekey.h"
 #include "send.h"
 
@@ -258,6 +259,31 @@ inline SendOwn send_own(Carver& c, size_t m, SendArgs& a) {
   return w;
 }
 inline size_t send_own_bytes(size_t m) { return measure(send_own, m); }
+
+// ------------------------------------------------------------ receive
+// Slice lengths, message ends, the kRecvSlotsAll jobs a payload (off, len, copy destination); then the
+// verify's status, the placement scan's per-payload output and the jobs' CRCs. Sized for ALL under either
+// flag. Walked under ASan + UBSan by tests/native/recv_asan.cpp.
+struct RecvOwn {
+  uint64_t* msg_end;                  // a.msg_end, a.vstatus, a.crc, writable
+  uint32_t *vstatus, *scan_out, *crc;
+};
+inline RecvOwn recv_own(Carver& c, size_t m, RecvArgs& a) {
+  RecvOwn w;
+  c.take_each(m, a.len, w.msg_end);
+  c.take_each((size_t)kRecvSlotsAll * m, a.job_off, a.job_len, a.copy_off);
+  c.take_each(m, w.vstatus, w.scan_out);
+  w.crc = c.take<uint32_t>((size_t)kRecvSlotsAll * m);
+  a.msg_end = w.msg_end;
+  a.vstatus = w.vstatus;
+  a.crc = w.crc;
+  c.align(256);
+  return w;
+}
+inline size_t recv_own_bytes(size_t m) { return measure(recv_own, m); }
+// The whole receive workspace: the own area, the verify's job arrays (ALL's parse), one batch scratch for
+// the placement scan and the CRC pass in turn.
+inline size_t recv_ws_bytes(size_t m) { return recv_own_bytes(m) + msg_jobs_bytes(m) + ws_need((size_t)kRecvSlotsAll * m); }
 
 // ------------------------------------------------------------ chain
 // Scan blocks of any [start, region_len) of a region at any address: the span plus a leading granule.

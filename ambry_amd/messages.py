@@ -471,3 +471,79 @@ def send_messages_dev(region, msg_off, flag: int, msg_size=None, out=None, strea
                                            ctypes.c_void_p(_stream_handle(stream))),
           "ambrycrc_send_messages_dev")
     return out, info, status
+
+
+# ------------------------------------------------------------------ receiving a GET (GetBlobOperation.handleBody)
+MSG_BAD_RANGE = 1 << 18  # AMBRYCRC_MSG_BAD_RANGE: the requested range does not lie inside the blob content
+
+RECV_NOWHERE = 0xFFFFFFFFFFFFFFFF  # ambrycrc_recv_info.out_off of a payload that delivers nothing
+RECV_TO_END = 0xFFFFFFFFFFFFFFFF   # a range's hi: to the content's end
+
+# numpy mirror of struct ambrycrc_recv_info (56 bytes): where the content went, BlobData's fields, and under
+# ALL the places of the encryption key, the BlobPropertiesSerDe bytes and the user metadata in the payload.
+RECV_INFO_DTYPE = np.dtype([("out_off", "<u8"), ("out_len", "<u8"), ("blob_size", "<u8"), ("content_rel", "<u4"),
+                            ("enckey_rel", "<u4"), ("enckey_len", "<u4"), ("props_rel", "<u4"), ("props_len", "<u4"),
+                            ("usermeta_rel", "<u4"), ("usermeta_len", "<u4"), ("blob_type", "u1"),
+                            ("compressed", "u1"), ("blob_version", "u1"), ("header_version", "u1")])
+assert RECV_INFO_DTYPE.itemsize == 56
+
+
+def receive_workspace_bytes(m: int) -> int:
+    return int(lib().ambrycrc_receive_workspace_size(m))
+
+
+def receive_blob_cpu(payload, flag: int, lo: int = 0, hi=None, out_cap=None):
+    """ambrycrc_receive_blob_cpu: deserializeBlob (SEND_BLOB: a bare blob record) or deserializeBlobAll
+    (SEND_ALL: a whole stored message) over one payload in host memory, the content sliced to [lo, hi)
+    (hi None: to the content's end). Returns (status bits, one RECV_INFO_DTYPE record, the delivered bytes;
+    None when refused)."""
+    buf = np.frombuffer(payload, dtype=np.uint8) if not isinstance(payload, np.ndarray) else payload
+    cap = out_cap if out_cap is not None else buf.size
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    info = np.zeros(1, dtype=RECV_INFO_DTYPE)
+    st = ctypes.c_uint32(0)
+    check(lib().ambrycrc_receive_blob_cpu(ctypes.c_void_p(buf.ctypes.data if buf.size else 0), buf.size, flag, int(lo),
+                                          RECV_TO_END if hi is None else int(hi), ctypes.c_void_p(out.ctypes.data),
+                                          cap, ctypes.c_void_p(info.ctypes.data), ctypes.byref(st)),
+          "ambrycrc_receive_blob_cpu")
+    got = None if int(info[0]["out_off"]) == RECV_NOWHERE else out[:int(info[0]["out_len"])].tobytes()
+    return st.value, info[0].copy(), got
+
+
+def receive_blobs_dev(body, pay_off, flag: int, pay_size=None, ranges=None, dst_off=None, out=None, stream=None,
+                      workspace=None):
+    """ambrycrc_receive_blobs_dev -- the router's GET receive for a batch of payloads of a GetResponse body in
+    HBM under SEND_BLOB or SEND_ALL: each blob record verified, its content sliced to the payload's range and
+    written to `out` (a uint8 CUDA tensor; default: the body's size). pay_off / pay_size: int64 CUDA tensors,
+    the out_off / send_len columns of the sending side (pay_size None: each payload runs to the body's end).
+    ranges: an int64 CUDA tensor of 2m elements (lo, hi per payload; hi -1: to the content's end) or None.
+    dst_off: an int64 CUDA tensor of m destinations in `out`, or None to pack in payload order. workspace: a
+    CUDA tensor of receive_workspace_bytes(m) bytes (needed to capture the call into a graph), or None.
+    Returns (out, info: a uint8 CUDA tensor holding the RECV_INFO_DTYPE array, status int32[m])."""
+    import torch
+
+    from .device import _stream_handle, _workspace
+
+    if body.dtype != torch.uint8 or not body.is_cuda:
+        raise TypeError("body must be a uint8 CUDA tensor")
+    dev = body.device
+    if pay_off.dtype != torch.int64 or not pay_off.is_cuda or not pay_off.is_contiguous() or pay_off.device != dev:
+        raise TypeError("pay_off must be a contiguous int64 CUDA tensor on the body's device")
+    m = pay_off.numel()
+    for name, t, n in (("pay_size", pay_size, m), ("ranges", ranges, 2 * m), ("dst_off", dst_off, m)):
+        if t is not None and (t.dtype != torch.int64 or not t.is_cuda or t.device != dev or not t.is_contiguous()
+                              or t.numel() != n):
+            raise TypeError(f"{name} must be a contiguous int64 CUDA tensor of {n} elements on the body's device")
+    if out is None:
+        out = torch.empty(max(body.numel(), 1), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.device != dev:
+        raise TypeError("out must be a contiguous uint8 CUDA tensor on the body's device")
+    info = torch.empty(m * RECV_INFO_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    status = torch.empty(m, dtype=torch.int32, device=dev)
+    ws, ws_bytes = _workspace(workspace, dev)
+    ptr = lambda t: None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    check(lib().ambrycrc_receive_blobs_dev(ptr(body), body.numel(), ptr(pay_off), ptr(pay_size), m, flag, ptr(ranges),
+                                           ptr(dst_off), ptr(out), out.numel(), ptr(info), ptr(status), ws, ws_bytes,
+                                           ctypes.c_void_p(_stream_handle(stream))),
+          "ambrycrc_receive_blobs_dev")
+    return out, info, status

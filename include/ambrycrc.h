@@ -514,6 +514,72 @@ int ambrycrc_send_messages_dev(const uint8_t* d_region, uint64_t region_len, con
 int ambrycrc_send_message_cpu(const uint8_t* region, uint64_t region_len, uint64_t off, uint64_t size /* 0: the header's */,
                               int flag, uint8_t* out, uint64_t out_cap, ambrycrc_send_info* info, uint32_t* status);
 
+/* ------------------------------------------------ receiving a GET: blob content out of a response body */
+
+/* The requested byte range does not lie inside the blob content: hi > the record's size with hi not
+ * UINT64_MAX, or lo > hi (hi == UINT64_MAX standing for the size, so lo > size is refused too). The library's own check: the reference's router resolves the range against the blob
+ * size before it slices (GetBlobOperation.java:1394-1412). */
+#define AMBRYCRC_MSG_BAD_RANGE (1u << 18)
+
+typedef struct ambrycrc_recv_info {   /* 56 bytes, no padding */
+  uint64_t out_off;      /* where the delivered content starts in d_out; UINT64_MAX: nothing delivered */
+  uint64_t out_len;      /* hi - lo */
+  uint64_t blob_size;    /* BlobData.getSize(): the record's size field */
+  uint32_t content_rel;  /* first content byte, relative to the payload */
+  uint32_t enckey_rel, enckey_len;       /* ALL: the key bytes (record + 6); 0 / 0 without the record. BLOB: 0 */
+  uint32_t props_rel, props_len;         /* ALL: the BlobPropertiesSerDe bytes. BLOB: 0 */
+  uint32_t usermeta_rel, usermeta_len;   /* ALL: the metadata bytes. BLOB: 0 */
+  uint8_t  blob_type, compressed, blob_version, header_version;  /* header_version 0 under BLOB */
+} ambrycrc_recv_info;
+
+/* The router's side of a GET (GetBlobOperation.handleBody, ambry-router/.../GetBlobOperation.java:1113-1141,
+ * :1615-1694) for m payloads of a GetResponse body in HBM: MessageFormatRecord.deserializeBlob (flag
+ * AMBRYCRC_SEND_BLOB: a payload is a bare Blob_Format_V1 / V2 / V3 record) or deserializeBlobAll
+ * (AMBRYCRC_SEND_ALL: a whole stored message) over each (MessageFormatRecord.java:222-241, :257-303,
+ * :1668-1833), then the blob content -- the bytes after the record's 10 / 12 / 13-byte head and before its
+ * CRC -- sliced to the request's range and written to d_out. d_pay_off[i] / d_pay_size[i] are
+ * ambrycrc_send_info.out_off / .send_len of the sending side (d_pay_size NULL: each payload runs to the
+ * body's end); the GetResponse framing around the body stays with the caller, and so does the store-key
+ * comparison. d_range (nullable, [2m]): lo, hi (exclusive) inside the content, hi == UINT64_MAX: to the
+ * content's end. d_dst_off (nullable, [m]): where each payload's slice goes in d_out -- chunks filed under
+ * their index; overlapping destinations are the caller's business. NULL: packed in payload order.
+ * d_status[i] is the first of these that applies (the CRC bits of step 6 accumulate):
+ *  1. AMBRYCRC_MSG_BAD_LAYOUT: the offset is at or past the body's end, a given size is 0, or off + size is
+ *     past the body.
+ *  2. BLOB, the record's own fields: AMBRYCRC_MSG_BAD_VERSION for an unknown record version;
+ *     AMBRYCRC_MSG_BAD_RECORD for fewer bytes than head + 8, a type ordinal >= 2 or a size above
+ *     Integer.MAX_VALUE; AMBRYCRC_MSG_BAD_LAYOUT when head + size + 8 passes the payload (the reference's
+ *     stream runs dry). Bytes after the record are not read.
+ *  3. ALL, the header inside the payload as ambrycrc_verify_messages_dev judges it (AMBRYCRC_MSG_BAD_VERSION /
+ *     _HEADER_CRC / _BAD_LAYOUT); AMBRYCRC_MSG_NOT_PUT for an update message ("Only 'put' records are valid");
+ *     then every record-check bit the verify reports (AMBRYCRC_MSG_BAD_VERSION / _BAD_RECORD), since
+ *     deserializeBlobAll throws for them.
+ *  4. AMBRYCRC_MSG_BAD_RANGE.
+ *  5. AMBRYCRC_MSG_NO_ROOM: packed, the slice does not fit below out_cap (the running offset still
+ *     advances); with d_dst_off, d_dst_off[i] + out_len > out_cap.
+ *  6. AMBRYCRC_MSG_BLOB_CRC, and under ALL also AMBRYCRC_MSG_ENCKEY_CRC / _PROPS_CRC / _USERMETA_CRC, all
+ *     that apply; a stored long with a non-zero upper word is a mismatch.
+ * A payload refused by 1-5 writes no byte of d_out, and its info is zero but for out_off = UINT64_MAX. One
+ * that fails only 6 reports its info; the bytes inside its destination span are unspecified (the pass
+ * copies while it hashes; the reference would have thrown), and nothing outside the span is written. A
+ * clean payload delivers content[lo, hi) and nothing else; an empty range or a blob of size 0 is clean with
+ * out_len 0. The whole record is hashed whatever the range. d_out must not overlap the body, which is only
+ * read. Only enqueues on `stream`, never synchronizes; may be captured into a HIP graph with a caller
+ * workspace (d_ws >= ambrycrc_receive_workspace_size(m)); d_ws NULL uses the stream's default workspace.
+ * (Not named *_workspace_bytes, as ambrycrc_ingest_puts_workspace_size is not: this one is pinned by
+ * tests/golden/recv_workspace_size.json.) */
+size_t ambrycrc_receive_workspace_size(size_t m);
+int ambrycrc_receive_blobs_dev(const uint8_t* d_body, uint64_t body_len, const uint64_t* d_pay_off,
+                               const uint64_t* d_pay_size /* nullable */, size_t m, int flag,
+                               const uint64_t* d_range /* nullable */, const uint64_t* d_dst_off /* nullable */,
+                               uint8_t* d_out, uint64_t out_cap, ambrycrc_recv_info* d_info, uint32_t* d_status,
+                               void* d_ws, size_t ws_bytes, hipStream_t stream);
+/* The same for one payload of `avail` bytes in host memory (the CLMUL loop, memcpy); hi UINT64_MAX: to the
+ * content's end. The slice starts at out (info->out_off 0); out NULL with bytes to deliver, or out_len >
+ * out_cap: AMBRYCRC_MSG_NO_ROOM. */
+int ambrycrc_receive_blob_cpu(const uint8_t* payload, uint64_t avail, int flag, uint64_t lo, uint64_t hi,
+                              uint8_t* out, uint64_t out_cap, ambrycrc_recv_info* info, uint32_t* status);
+
 /* ------------------------------------- log-region recovery: message chain and MessageInfo */
 
 /* Status bit the recover entries add to the verify bits: a verified message whose operation time (a PUT's
