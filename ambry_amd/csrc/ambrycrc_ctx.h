@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <atomic>
 #include <mutex>
@@ -251,6 +252,24 @@ PlanArgs plan_scan_args(const uint64_t* off, const uint64_t* len, size_t n, void
 int enqueue_scan_copy(DevCtx* c, const uint64_t* src, const uint64_t* dst_off, const uint64_t* len,
                       const uint64_t* cost, size_t n, uint8_t* dst, void* scratch, uint32_t* out,
                       const uint32_t* gate, hipStream_t s);
+// Packed placement of m messages of out_len[i] bytes: that scan over the lengths (off: any [m] device array,
+// the plan's chunk offsets), then the transform's place step -- desc[i].out_off and out_off[i], or for a
+// message past out_cap NO_ROOM in status[i], header_version 0 and out_len[i] 0 (it still advances the
+// running offset).
+inline int enqueue_place(const uint64_t* off, ::ambrycrc_put_desc* desc, uint64_t* out_len, uint64_t* out_off,
+                         uint32_t* status, size_t m, uint64_t out_cap, void* scratch, uint32_t* scan_out, hipStream_t s) {
+  const PlanArgs p = plan_scan_args(off, out_len, m, scratch, scan_out);
+  if (launch_plan(p, s) != hipSuccess) return AMBRYCRC_EHIP;
+  TransformArgs t;
+  memset(&t, 0, sizeof t);
+  t.m = m;
+  t.desc = desc;
+  t.out_len = out_len;
+  t.out_off = out_off;
+  t.status = status;
+  t.out_cap = out_cap;
+  return launch_transform_place(t, p.byte_start, s) == hipSuccess ? AMBRYCRC_OK : AMBRYCRC_EHIP;
+}
 // Plan + CRC kernels for n chunks on stream s (ws: >= ws_need(n) bytes). exp_fill, copy_dst,
 // copy_off: see SweepArgs (copy_dst set: the copy-through kernel, whatever c's variant).
 int enqueue_batch(DevCtx* c, const uint8_t* base, const uint64_t* off, const uint64_t* len, const uint32_t* crc_in,

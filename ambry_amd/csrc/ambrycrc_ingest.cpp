@@ -13,6 +13,7 @@
 #include "ambrycrc_ctx.h"
 #include "crc32_gf2.h"
 #include "crc32_kernels.h"
+#include "put_emit.h"
 #include "put_request.h"
 
 using namespace ambrycrc;
@@ -80,17 +81,8 @@ int ambrycrc_ingest_put_requests_dev(const uint8_t* d_wire, uint64_t wire_len, c
   if (launch_ingest_verdict(a, c->num_cu, stream) != hipSuccess) return AMBRYCRC_EHIP;
   // 4. packed placement: exclusive scan of the lengths, then the transform's place step (NO_ROOM for
   //    a message past out_cap, which still advances the running offset)
-  const PlanArgs p = plan_scan_args(a.job_off, d_out_len, m, shared, w.scan_out);
-  if (launch_plan(p, stream) != hipSuccess) return AMBRYCRC_EHIP;
-  TransformArgs t;
-  memset(&t, 0, sizeof t);
-  t.m = m;
-  t.desc = a.desc;
-  t.out_len = d_out_len;
-  t.out_off = d_out_off;
-  t.status = d_status;
-  t.out_cap = out_cap;
-  if (launch_transform_place(t, p.byte_start, stream) != hipSuccess) return AMBRYCRC_EHIP;
+  rc = enqueue_place(a.job_off, a.desc, d_out_len, d_out_off, d_status, m, out_cap, shared, w.scan_out, stream);
+  if (rc) return rc;
   // 5. header, record heads, properties, every trailer, the MessageInfo, the packed length (zeroed
   //    by the verdict kernel)
   if (launch_ingest_write(a, c->num_cu, stream) != hipSuccess) return AMBRYCRC_EHIP;
@@ -123,25 +115,16 @@ int ambrycrc_ingest_put_request_cpu(const uint8_t* wire, uint64_t wire_len, cons
     *status = AMBRYCRC_MSG_NO_ROOM;
     return AMBRYCRC_OK;
   }
+  // bodies in place, then every trailer hashed from the output
   put_write_fixed(d, L, out);
-  put_be64(out + L.hsize - 8, (uint64_t)ambrycrc_update(0, out, L.hsize - 8));
   if (d.key_len) memcpy(out + L.hsize, wire + d.key_src, d.key_len);
-  if (L.enc_rec) {
-    uint8_t* q = out + L.enc_rel;
-    memcpy(q + 6, wire + d.enckey_src, (size_t)d.enckey_len);
-    put_be64(q + 6 + d.enckey_len, (uint64_t)ambrycrc_update(0, q, 6ull + (uint64_t)d.enckey_len));
-  }
+  if (L.enc_rec) memcpy(out + L.enc_rel + 6, wire + d.enckey_src, (size_t)d.enckey_len);
   const PropsFix x = ingest_props_fix(p);
   uint8_t* ps = out + L.bp_rel + 2;
-  for (uint32_t j = 0; j < d.props_len; ++j)
-    ps[j] = ingest_props_byte(x, j, j < x.stored_len ? wire[d.props_src + j] : 0);
-  put_be64(ps + d.props_len, (uint64_t)ambrycrc_update(0, out + L.bp_rel, 2ull + d.props_len));
-  uint8_t* um = out + L.um_rel;
-  if (d.usermeta_len) memcpy(um + 6, wire + d.usermeta_src, d.usermeta_len);
-  put_be64(um + 6 + d.usermeta_len, (uint64_t)ambrycrc_update(0, um, 6ull + d.usermeta_len));
-  uint8_t* bl = out + L.blob_rel;
-  if (d.blob_len) memcpy(bl + 13, wire + d.blob_src, d.blob_len);
-  put_be64(bl + 13 + d.blob_len, (uint64_t)ambrycrc_update(0, bl, 13ull + d.blob_len));
+  for (uint32_t j = 0; j < d.props_len; ++j) ps[j] = props_v5_byte(x, j, j < x.stored_len ? wire[d.props_src + j] : 0);
+  if (d.usermeta_len) memcpy(out + L.um_rel + 6, wire + d.usermeta_src, d.usermeta_len);
+  if (d.blob_len) memcpy(out + L.blob_rel + 13, wire + d.blob_src, d.blob_len);
+  for (uint32_t k = 0; k < kPutSlots; ++k) put_seal_record(out, L, k);
   if (info) ingest_info(wire, p, d, L, 0, info);
   *out_len = L.length;
   return AMBRYCRC_OK;

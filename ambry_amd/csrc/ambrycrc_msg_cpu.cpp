@@ -11,6 +11,7 @@
 
 #include "hard_delete.h"
 #include "msg_header.h"
+#include "put_emit.h"
 #include "put_layout.h"
 #include "record_fields.h"
 #include "recover.h"
@@ -77,7 +78,7 @@ uint32_t transform_plan(const uint8_t* region, uint64_t region_len, uint64_t off
   const uint32_t st = off <= region_len ? verify(region + off, region_len - off, &H, &end) : (uint32_t)AMBRYCRC_MSG_BAD_LAYOUT;
   if (st) return st;
   const uint8_t* p = region + off;
-  const int32_t enc = H.rel[0], bp = H.rel[1], upd = H.rel[2], um = H.rel[3], blob = H.rel[4];
+  const int32_t bp = H.rel[1], upd = H.rel[2], um = H.rel[3], blob = H.rel[4];
   if (upd != -1 || bp == -1 || um == -1 || blob == -1) return AMBRYCRC_MSG_NOT_PUT;  // "cannot be anything rather than put record"
   // the deserializers' field reads (deserializeBlobEncryptionKey / Properties / UserMetadata / Blob,
   // MessageFormatRecord.java:1568-1833; msg_header.h put_fields); verify's record checks already hold for them
@@ -88,35 +89,19 @@ uint32_t transform_plan(const uint8_t* region, uint64_t region_len, uint64_t off
   if (!f.ok || ambrycrc::props_parse<true>(p + bp + 2, stored, &pf) != 0) return AMBRYCRC_MSG_BAD_RECORD;
   if (!pf.ascii) return AMBRYCRC_MSG_NOT_ENCODABLE;
   x->fx = ambrycrc::props_fix_of(pf, stored);
-  // A V3 message with a V3 blob record and properties already canonical VERSION_5 bytes re-serializes
-  // at V3 to its own bytes but for the life version and the header CRC (the GPU fast path's rule,
+  // A V3 message with a V3 blob record (isCompressed 0 or 1) and properties already canonical VERSION_5
+  // bytes re-serializes at V3 to its own bytes but for the life version and the header CRC (the GPU fast path's rule,
   // region_proc.h transform_fast): one copy and the 32-byte header's CRC, instead of the layout,
   // copy and every record CRC again.
-  if (header_version == 3 && H.version == 3 && f.blob_version == 3 && x->fx.version == 0) {
+  if (header_version == 3 && H.version == 3 && f.blob_version == 3 && p[blob + 4] <= 1 && x->fx.version == 0) {
     x->fast = true;
     x->len = end;
     x->life = have_life && (uint16_t)life_version != (uint16_t)H.life ? (int)(uint16_t)life_version : -1;
     return 0;
   }
-  ambrycrc_put_desc& d = x->d;
-  memset(&d, 0, sizeof d);
-  const bool keep_enc = enc != -1 && header_version >= 2;
-  d.out_off = 0;
-  d.key_src = off + H.hs;
-  d.key_len = (uint32_t)(f.first - H.hs);
-  d.enckey_src = keep_enc ? off + enc + 6 : 0;
-  d.enckey_len = keep_enc ? (int32_t)f.enc_len : -1;
-  d.props_src = off + bp + 2;
-  d.props_len = ambrycrc::props_v5_len(x->fx);
-  d.usermeta_src = off + um + 6;
-  d.usermeta_len = f.um_len;
-  d.blob_src = off + blob + f.head;
-  d.blob_len = f.size;
-  d.life_version = (int16_t)(have_life ? life_version : H.life);
-  d.blob_type = (int16_t)f.type;
-  d.compressed = (uint8_t)f.comp;
-  d.header_version = (uint8_t)header_version;
-  x->len = ambrycrc_put_layout(&d, nullptr);
+  x->d = ambrycrc::put_desc_of_stored(off, H, f, header_version, have_life ? life_version : H.life,
+                                      ambrycrc::props_v5_len(x->fx));
+  x->len = ambrycrc_put_layout(&x->d, nullptr);
   return x->len ? 0u : (uint32_t)AMBRYCRC_MSG_BAD_RECORD;
 }
 
@@ -135,12 +120,10 @@ int transform_emit(const uint8_t* region, uint64_t off, const XPlan& x, uint8_t*
   // record CRC recomputed
   const int rc = ambrycrc_serialize_put_host(&x.d, region, region, out, x.len, nullptr);
   if (rc) return rc;
-  if (x.fx.version) {
-    uint64_t fo[5];
-    ambrycrc_put_layout(&x.d, fo);
-    uint8_t* rec = out + fo[2] - 2;
-    ambrycrc::props_apply_fix(rec + 2, x.fx);
-    ambrycrc::put_be64(rec + 2 + x.d.props_len, (uint64_t)ambrycrc_update(0, rec, 2ull + x.d.props_len));
+  ambrycrc::PutLayout L;
+  if (x.fx.version && ambrycrc::put_layout(x.d, L)) {
+    ambrycrc::props_apply_fix(out + L.bp_rel + 2, x.fx);
+    ambrycrc::put_seal_record(out, L, 2);
   }
   return AMBRYCRC_OK;
 }
@@ -325,18 +308,17 @@ int ambrycrc_rekey_message_cpu(const uint8_t* region, uint64_t region_len, uint6
     return AMBRYCRC_OK;
   }
   const bool repl = r.content_src != ambrycrc::kRekeyKeep;
+  // bodies in place (the encryption-key and user-metadata records whole, their trailers verified), then the
+  // header's, the properties' and the blob record's trailers hashed from the output
   ambrycrc::put_write_fixed(d, L, out);
-  ambrycrc::put_be64(out + L.hsize - 8, (uint64_t)ambrycrc_update(0, out, L.hsize - 8));
   memcpy(out + L.hsize, aux + d.key_src, d.key_len);
-  if (L.enc_rec) memcpy(out + L.enc_rel, region + d.enckey_src - 6, L.enc_rec);  // the record whole, trailer verified
+  if (L.enc_rec) memcpy(out + L.enc_rel, region + d.enckey_src - 6, L.enc_rec);
   uint8_t* ps = out + L.bp_rel + 2;
   for (uint32_t j = 0; j < d.props_len; ++j)
     ps[j] = ambrycrc::rekey_props_byte(x, r, j, j < x.stored_len ? region[d.props_src + j] : 0);
-  ambrycrc::put_be64(ps + d.props_len, (uint64_t)ambrycrc_update(0, out + L.bp_rel, 2ull + d.props_len));
   memcpy(out + L.um_rel, region + d.usermeta_src - 6, L.um_rec);
-  uint8_t* bc = out + L.blob_rel + 13;
-  if (d.blob_len) memcpy(bc, (repl ? aux : region) + d.blob_src, d.blob_len);
-  ambrycrc::put_be64(bc + d.blob_len, (uint64_t)ambrycrc_update(0, out + L.blob_rel, 13ull + d.blob_len));
+  if (d.blob_len) memcpy(out + L.blob_rel + 13, (repl ? aux : region) + d.blob_src, d.blob_len);
+  for (uint32_t k = 0; k < ambrycrc::kPutSlots; k += 2) ambrycrc::put_seal_record(out, L, k);
   *out_len = L.length;
   return AMBRYCRC_OK;
 }

@@ -9,6 +9,7 @@
 #include "../../include/ambrycrc.h"
 #include "ambrycrc_ctx.h"
 #include "crc32_kernels.h"
+#include "put_emit.h"
 #include "put_layout.h"
 #include "record_fields.h"
 
@@ -126,11 +127,7 @@ int ambrycrc_serialize_put_host(const ambrycrc_put_desc* d, const uint8_t* field
   }
   put_write_fixed(*d, L, m);
   for (uint32_t k = 0; k < kPutSlots; ++k) {
-    uint64_t off, ln;
-    bool present;
-    put_crc_job(L, k, &off, &ln, &present);
-    const uint32_t c = present ? ambrycrc_update(0, m + off, ln) : 0u;
-    if (present) put_be64(m + off + ln, (uint64_t)c);
+    const uint32_t c = put_seal_record(m, L, k);
     if (crcs) crcs[k] = c;
   }
   return AMBRYCRC_OK;

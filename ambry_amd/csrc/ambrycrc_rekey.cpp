@@ -73,17 +73,8 @@ int ambrycrc_rekey_messages_dev(const uint8_t* d_region, uint64_t region_len, co
   if (launch_rekey_plan(a, c->num_cu, stream) != hipSuccess) return AMBRYCRC_EHIP;
   // 3. packed placement: exclusive scan of the lengths, then the transform's place step (NO_ROOM
   //    for a message past out_cap, which still advances the running offset)
-  const PlanArgs p = plan_scan_args(d_msg_off, d_out_len, m, shared, w.scan_out);
-  if (launch_plan(p, stream) != hipSuccess) return AMBRYCRC_EHIP;
-  TransformArgs t;
-  memset(&t, 0, sizeof t);
-  t.m = m;
-  t.desc = a.desc;
-  t.out_len = d_out_len;
-  t.out_off = d_out_off;
-  t.status = d_status;
-  t.out_cap = out_cap;
-  if (launch_transform_place(t, p.byte_start, stream) != hipSuccess) return AMBRYCRC_EHIP;
+  rc = enqueue_place(d_msg_off, a.desc, d_out_len, d_out_off, d_status, m, out_cap, shared, w.scan_out, stream);
+  if (rc) return rc;
   // 4. the replacement contents' CRCs (one job a message over aux; most are empty and read nothing),
   //    then header, record heads, properties and every trailer
   rc = enqueue_batch(c, a.aux, a.cjob_off, a.cjob_len, nullptr, w.ccrc, m, shared, stream);

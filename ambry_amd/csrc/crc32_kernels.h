@@ -276,6 +276,7 @@ struct PutArgs {
 // (~2 us, ~1.6 KB of its share of HBM bandwidth) per job whatever its size, so balancing bytes
 // alone put 22,000 24-B key copies on one wave (a 28 ms kernel for 4 GiB of 64 KiB PUTs).
 constexpr uint64_t kCopyJobCost = 2048;
+__host__ __device__ inline uint64_t copy_job_cost(uint64_t len) { return len ? len + kCopyJobCost : 0; }
 
 struct CopyArgs {
   const uint64_t* src;      // [n] absolute source addresses

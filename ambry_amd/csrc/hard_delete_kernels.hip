@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void hd_seal_kernel(HdArgs a) {
     // the blobs (slot-major put 65,536 1000-B jobs on 47 waves: 1.33 ms against 1.06 for 64 KiB blobs)
     a.fill_off[2 * i + k] = fo[k];
     a.fill_len[2 * i + k] = fl[k];
-    a.fill_cost[2 * i + k] = fl[k] ? fl[k] + kCopyJobCost : 0;
+    a.fill_cost[2 * i + k] = copy_job_cost(fl[k]);
   }
 }
 

@@ -27,6 +27,7 @@
 #include "crc32_kernels.h"
 #include "crc32_layout.h"
 #include "crc_img.h"
+#include "put_emit.h"
 #include "put_layout.h"
 #include "put_request.h"
 #include "record_fields.h"
@@ -87,12 +88,9 @@ __global__ __launch_bounds__(256) void ingest_verdict_kernel(IngestArgs a) {
   }
 }
 
-// One CRC step over byte b through the LDS byte table (t[0..255] = T0, stage_slice_tables).
-__device__ __forceinline__ uint32_t ingest_crc_step(const uint32_t* __restrict__ t, uint32_t c, uint32_t b) {
-  return t[(c ^ b) & 0xffu] ^ (c >> 8);
-}
-
-__global__ __launch_bounds__(256) void ingest_write_kernel(IngestArgs a) {
+// Five waves a SIMD, as before the writers were shared (put_emit.h): left to itself the allocator takes two or
+// three VGPRs past the 96 that allow them.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void ingest_write_kernel(IngestArgs a) {
   __shared__ uint32_t tbl[1024];
   stage_slice_tables(tbl, a.img);
   __syncthreads();
@@ -108,75 +106,15 @@ __global__ __launch_bounds__(256) void ingest_write_kernel(IngestArgs a) {
       const IngestPlan p = a.plan[i];
       uint8_t* msg = a.out + d.out_off;
       top = d.out_off + L.length;
-      {  // header and its CRC, from the bytes in registers
-        uint8_t h[32];
-        const uint32_t hn = put_header_bytes(d, L, h);
-        if (hn == 32) __builtin_memcpy(msg, h, 32);
-        else if (hn == 30) __builtin_memcpy(msg, h, 30);
-        else __builtin_memcpy(msg, h, 26);
-        put_be64(msg + hn, (uint64_t)crc_regs_lds(tbl, 0u, h, hn));
-      }
-      uint8_t b[16];
-      // a record of head || body: crc = crc(head) x^(8|body|) + crc(body), the body hashed on the wire
-      if (L.enc_rec) {
-        put_prefix_bytes(d, 1, b);
-        uint8_t* q = msg + L.enc_rel;
-        __builtin_memcpy(q, b, 6);
-        const uint32_t c = mul_xpow8_img(a.img, crc_regs_lds(tbl, 0u, b, 6u), (uint64_t)d.enckey_len) ^ a.seg[3 * m + i];
-        put_be64(q + 6 + d.enckey_len, (uint64_t)c);
-      }
-      {  // BlobProperties_Format_V1: version 1, the VERSION_5 bytes, their CRC -- 8 B at a time
-        const PropsFix x = ingest_props_fix(p);
-        const uint8_t* ps = a.wire + d.props_src;
-        uint8_t* pd = msg + L.bp_rel;
-        put_be16(pd, 1u);
-        pd += 2;
-        uint32_t c = ingest_crc_step(tbl, ingest_crc_step(tbl, 0xFFFFFFFFu, 0u), 1u);
-        const uint32_t n = d.props_len;
-        for (uint32_t j0 = 0; j0 < n; j0 += 8) {
-          uint64_t w = 0;
-          if (j0 + 8 <= x.stored_len) {
-            __builtin_memcpy(&w, ps + j0, 8);
-          } else {
-#pragma unroll
-            for (uint32_t k = 0; k < 8; ++k)
-              if (j0 + k < x.stored_len) w |= (uint64_t)ps[j0 + k] << (8 * k);
-          }
-          uint64_t o = 0;
-#pragma unroll
-          for (uint32_t k = 0; k < 8; ++k) {
-            if (j0 + k < n) {
-              const uint32_t v = ingest_props_byte(x, j0 + k, (uint8_t)(w >> (8 * k)));
-              o |= (uint64_t)v << (8 * k);
-              c = ingest_crc_step(tbl, c, v);
-            }
-          }
-          if (j0 + 8 <= n) {
-            __builtin_memcpy(pd + j0, &o, 8);
-          } else {
-#pragma unroll
-            for (uint32_t k = 0; k < 8; ++k)
-              if (j0 + k < n) pd[j0 + k] = (uint8_t)(o >> (8 * k));
-          }
-        }
-        put_be64(pd + n, (uint64_t)~c);
-      }
-      {  // UserMetadata_Format_V1
-        put_prefix_bytes(d, 3, b);
-        uint8_t* q = msg + L.um_rel;
-        __builtin_memcpy(q, b, 6);
-        uint32_t c = crc_regs_lds(tbl, 0u, b, 6u);
-        if (d.usermeta_len) c = mul_xpow8_img(a.img, c, (uint64_t)d.usermeta_len) ^ a.seg[2 * m + i];
-        put_be64(q + 6 + d.usermeta_len, (uint64_t)c);
-      }
-      {  // Blob_Format_V3
-        put_prefix_bytes(d, 4, b);
-        uint8_t* q = msg + L.blob_rel;
-        __builtin_memcpy(q, b, 13);
-        uint32_t c = crc_regs_lds(tbl, 0u, b, 13u);
-        if (d.blob_len) c = mul_xpow8_img(a.img, c, d.blob_len) ^ a.seg[4 * m + i];
-        put_be64(q + 13 + d.blob_len, (uint64_t)c);
-      }
+      put_emit_header<true>(tbl, d, L, msg);
+      // each record of head || body from its head and the body's CRC, hashed on the wire; the properties
+      // written again at VERSION_5 and hashed from the bytes written
+      if (L.enc_rec) put_emit_record<1>(tbl, a.img, d, L, msg, &a.seg[3 * m + i]);
+      const PropsFix x = ingest_props_fix(p);
+      put_emit_props(tbl, a.wire + d.props_src, x.stored_len, msg + L.bp_rel, d.props_len,
+                     [&](uint32_t j, uint8_t stored) { return props_v5_byte(x, j, stored); });
+      put_emit_record<3>(tbl, a.img, d, L, msg, &a.seg[2 * m + i]);
+      put_emit_record<4>(tbl, a.img, d, L, msg, &a.seg[4 * m + i]);
       ingest_info(a.wire, p, d, L, d.out_off, &info);
       src[0] = (uint64_t)(uintptr_t)(a.wire + d.key_src);
       dst[0] = d.out_off + L.hsize;
@@ -194,13 +132,7 @@ __global__ __launch_bounds__(256) void ingest_write_kernel(IngestArgs a) {
       len[3] = d.blob_len;
     }
     if (a.info) a.info[i] = info;
-#pragma unroll
-    for (uint32_t k = 0; k < kIngestSlots; ++k) {
-      a.cp_src[k * m + i] = src[k];
-      a.cp_dst[k * m + i] = dst[k];
-      a.cp_len[k * m + i] = len[k];
-      a.cp_cost[k * m + i] = len[k] ? len[k] + kCopyJobCost : 0;
-    }
+    store_copy_jobs(a.cp_src, a.cp_dst, a.cp_len, a.cp_cost, m, i, src, dst, len);
   }
   if (a.total) {  // every lane is back from its loop: one atomic a wave that placed something
     const uint64_t w = wave_max_u64(top);

@@ -21,6 +21,7 @@
 #include "crc32_kernels.h"
 #include "crc32_layout.h"
 #include "crc_img.h"
+#include "put_emit.h"
 #include "put_layout.h"
 #include "msg_parse.h"
 #include "record_fields.h"
@@ -254,8 +255,9 @@ __device__ __forceinline__ uint32_t props_v5_crc(const uint32_t* __restrict__ im
                          L - (2ull + x.enc_pos + 1));
   }
   uint8_t app[kPropsAppendixMax];
-  const uint32_t na = props_appendix(x.version, app);
-  return crc_bytes_img(img, c, app, na);
+#pragma unroll
+  for (uint32_t k = 0; k < kPropsAppendixMax; ++k) app[k] = props_appendix_byte(x.version, k);
+  return crc_bytes_img(img, c, app, props_appendix_len(x.version));
 }
 
 // After the stored payloads are in place in the output: rewrite the re-encoded ones as V5.
@@ -280,16 +282,12 @@ __device__ __forceinline__ void transform_describe(const TransformArgs& a, uint6
     const uint64_t off = a.msg_off[i];
     const uint8_t* p = a.region + off;
     const MsgHeader H = msg_header_of(p);
-    const uint32_t hs = H.hs;
-    const int32_t enc = H.rel[0], bp = H.rel[1], upd = H.rel[2], um = H.rel[3], blob = H.rel[4];
+    const int32_t bp = H.rel[1], upd = H.rel[2], um = H.rel[3], blob = H.rel[4];
     if (upd != -1 || bp == -1 || um == -1 || blob == -1) {
       st |= AMBRYCRC_MSG_NOT_PUT;
     } else {
       // the deserializers' field reads against the header's spans (msg_header.h put_fields)
       const PutFields f = put_fields(p, H);
-      const int64_t first = f.first, end = f.end;  // message end, relative
-      const uint32_t head = f.head, type = f.type, comp = f.comp, bv = f.blob_version;
-      const uint64_t size = f.size;
       bool ok = f.ok;
       // deserializeBlobProperties -> serializeBlobProperties at VERSION_5 (record_fields.h)
       PropsFields pf;
@@ -302,46 +300,25 @@ __device__ __forceinline__ void transform_describe(const TransformArgs& a, uint6
       } else if (!encodable) {
         st |= AMBRYCRC_MSG_NOT_ENCODABLE;
       } else {
-        d.key_src = off + hs;
-        d.key_len = (uint32_t)(first - hs);
-        const bool keep_enc = enc != -1 && a.header_version >= 2;
-        d.enckey_src = keep_enc ? off + enc + 6 : 0;
-        d.enckey_len = keep_enc ? (int32_t)f.enc_len : -1;
-        d.props_src = off + bp + 2;
-        d.props_len = props_v5_len(fx);
+        d = put_desc_of_stored(off, H, f, a.header_version, a.life ? a.life[i] : H.life, props_v5_len(fx));
         a.pfix[i] = fx;
-        d.usermeta_src = off + um + 6;
-        d.usermeta_len = f.um_len;
-        d.blob_src = off + blob + head;
-        d.blob_len = size;
-        d.life_version = a.life ? a.life[i] : (int16_t)H.life;
-        d.blob_type = (int16_t)type;
-        d.compressed = (uint8_t)comp;
-        d.header_version = (uint8_t)a.header_version;
         PutLayout L;
         out_len = put_layout(d, L) ? L.length : 0;
         if (!out_len) {
           d.header_version = 0;
           st |= AMBRYCRC_MSG_BAD_RECORD;
         } else if (a.in_crc) {
-          // every record of the input verified: its CRC is the low word of its 8-B trailer
+          // every record of the input verified: its CRC is the low word of its 8-B trailer; the blob
+          // record's moves with its head (put_emit.h)
           uint32_t* ic = a.in_crc + 4 * i;
-          ic[0] = keep_enc ? ld_be32(p + bp - 4) : 0u;
+          ic[0] = L.enc_rec ? ld_be32(p + bp - 4) : 0u;
           ic[1] = props_v5_crc(a.img, p + bp, fx, ld_be32(p + um - 4));
           ic[2] = ld_be32(p + blob - 4);
-          uint32_t cblob = ld_be32(p + end - 4);
-          if (bv != 3) {  // the V3 head (version 3, type, compressed, size) replaces a V1/V2 head
-            // crc(B||C) = crc(A||C) ^ (crc(A) ^ crc(B)) * x^(8|C|)  (zlib's crc32_combine)
-            uint8_t h3[13];
-            put_be16(h3, 3u);
-            put_be16(h3 + 2, type);
-            h3[4] = (uint8_t)comp;
-            put_be64(h3 + 5, size);
-            const uint32_t ca = crc_bytes_img(a.img, 0u, p + blob, head);
-            const uint32_t cb = crc_bytes_img(a.img, 0u, h3, 13);
-            cblob ^= mul_xpow8_img(a.img, ca ^ cb, size);
-          }
-          ic[3] = cblob;
+          uint8_t h3[16];
+          put_prefix_bytes(d, 4, h3);
+          const uint32_t* img = a.img;
+          ic[3] = blob_crc_moved([&](const uint8_t(&b)[16], uint32_t n) { return crc_bytes_img(img, 0u, b, n); }, img,
+                                 p + blob, f.head, h3, ld_be32(p + f.end - 4), f.size);
         }
       }
     }

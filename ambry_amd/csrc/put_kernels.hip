@@ -22,6 +22,7 @@
 #include "crc32_layout.h"
 #include "crc_img.h"
 #include "crc_wave.h"
+#include "put_emit.h"
 #include "put_layout.h"
 #include "record_fields.h"
 #include "region_crc.h"
@@ -86,12 +87,7 @@ __global__ __launch_bounds__(256) void put_layout_kernel(PutArgs a) {
   }
   uint8_t* msg = a.out + d.out_off;
   put_write_fixed(d, L, msg);
-  uint32_t head_crc = 0;
-  if (hashes) {
-    uint8_t h[32];
-    const uint32_t hn = put_header_bytes(d, L, h);
-    head_crc = crc_regs_lds(tbl, 0u, h, hn);
-  }
+  if (hashes) put_emit_header<false>(tbl, d, L, msg);  // (the header's trailer: in both modes that hash)
   uint64_t fo[5];
   put_field_offsets(d, L, fo);
   const uint64_t src[5] = {d.key_src, d.enckey_src, d.props_src, d.usermeta_src, d.blob_src};
@@ -106,21 +102,17 @@ __global__ __launch_bounds__(256) void put_layout_kernel(PutArgs a) {
                                : (a.copy_through ? (uint64_t)(uintptr_t)(msg + fo[k]) - a.src_base : 0);
     a.cp_dst[k * m + i] = d.out_off + fo[k];
     a.cp_len[k * m + i] = base || a.copy_through ? len[k] : 0;
-    a.cp_cost[k * m + i] = base && len[k] ? len[k] + kCopyJobCost : 0;
+    a.cp_cost[k * m + i] = base ? copy_job_cost(len[k]) : 0;
     uint64_t off, ln;
     bool present;
     put_crc_job(L, k, &off, &ln, &present);
     a.crc_off[k * m + i] = d.out_off + off;
     a.crc_len[k * m + i] = present ? ln : 0;
-    if (a.in_crc && present) {  // transform: every CRC known but the header's (hashed here)
-      const uint32_t crc = k == 0 ? head_crc : a.in_crc[4 * i + k - 1];
-      put_be64(msg + off + ln, (uint64_t)crc);
-    }
-    if (a.copy_through) {  // the batch's seeds: each record's prefix CRC; the header is hashed whole
+    // transform: every record's CRC known
+    if (a.in_crc && present && k) put_be64(msg + off + ln, (uint64_t)a.in_crc[4 * i + k - 1]);
+    if (a.copy_through) {  // the batch's seeds: each record's prefix CRC (the header is hashed whole, above)
       uint32_t seed = 0;
-      if (k == 0) {
-        put_be64(msg + ln, (uint64_t)head_crc);
-      } else if (present) {
+      if (k && present) {
         uint8_t b[16];
         const uint32_t pl = put_prefix_bytes(d, k, b);
         seed = crc_regs_lds(tbl, 0u, b, pl);
@@ -393,9 +385,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(AMBRY_REGIO
     // message i's run slots, addressed by base-relative run index (record_crc's rk[k])
     const uint32_t* rk = reinterpret_cast<const uint32_t*>(
         reinterpret_cast<uintptr_t>(a.rk + kRunPad + i * kStreamPutRuns) - ((m0 >> 6) << 2));
-    uint8_t h[32];
-    const uint32_t hn = put_header_bytes(d, L, h);
-    put_be64(msg + hn, (uint64_t)crc_regs_lds(tbl, 0u, h, hn));
+    put_emit_header<false>(tbl, d, L, msg);
 #pragma unroll 1
     for (uint32_t k = 1; k < kPutSlots; ++k) {
       uint64_t off, ln;

@@ -131,14 +131,19 @@ __host__ __device__ inline int32_t put_record_rel(const PutLayout& L, uint32_t k
   return k == 1 ? L.enc_rel : k == 2 ? L.bp_rel : k == 3 ? L.um_rel : L.blob_rel;
 }
 
-// Header (without its CRC) and the fixed prefixes of every record, at message start m
-// (constant-size copies: on the device one wide unaligned store per 16 B, not a store per byte).
-__host__ __device__ inline void put_write_fixed(const ambrycrc_put_desc& d, const PutLayout& L, uint8_t* m) {
-  uint8_t h[32];
-  const uint32_t n = put_header_bytes(d, L, h);
+// The n = 32, 30 or 26 header bytes of put_header_bytes at message start m (constant-size copies: on the
+// device one wide unaligned store per 16 B, not a store per byte).
+__host__ __device__ inline void put_store_header(uint8_t* m, const uint8_t (&h)[32], uint32_t n) {
   if (n == 32) __builtin_memcpy(m, h, 32);
   else if (n == 30) __builtin_memcpy(m, h, 30);
   else __builtin_memcpy(m, h, 26);
+}
+
+// Header (without its CRC) and the fixed prefixes of every record, at message start m (constant-size
+// copies, as the header's).
+__host__ __device__ inline void put_write_fixed(const ambrycrc_put_desc& d, const PutLayout& L, uint8_t* m) {
+  uint8_t h[32];
+  put_store_header(m, h, put_header_bytes(d, L, h));
   uint8_t b[16];
   if (L.enc_rec) {
     put_prefix_bytes(d, 1, b);

@@ -198,18 +198,6 @@ __host__ __device__ inline PropsFix ingest_props_fix(const IngestPlan& p) {
   return props_fix_of(f, p.props_len);
 }
 
-// Byte j of the VERSION_5 payload from the wire payload's byte j (`stored`; anything when j >=
-// stored_len): the transform's re-encoding (record_fields.h props_apply_fix), a byte at a time.
-__host__ __device__ inline uint8_t ingest_props_byte(const PropsFix& x, uint32_t j, uint8_t stored) {
-  if (!x.version) return stored;
-  uint8_t b = j < x.stored_len ? stored : (x.version == 1 && j - x.stored_len < 4 ? 0xFF : 0);
-  if (j == 0) b = 0;
-  else if (j == 1) b = 5;
-  else if (j == kSerdePrivate) b = x.priv;
-  else if (x.enc_pos && j == x.enc_pos) b = x.enc;
-  return b;
-}
-
 // After the parse, with the computed wire CRC: 0 and the output's put descriptor (every source an
 // offset in the wire buffer, out_off left 0), or the first refusal of
 //   WIRE_CRC       computed CRC != the stored long, high word included (:457-460)

@@ -177,11 +177,12 @@ __host__ __device__ inline uint32_t update_record_check(const uint8_t* q, uint64
 // throws (ValidatingTransformer.java:100-102). UTF-8 default charset assumed.
 constexpr uint32_t kPropsAppendixMax = 17;
 
-__host__ __device__ inline uint32_t props_appendix(uint32_t version, uint8_t (&a)[kPropsAppendixMax]) {
-  const uint32_t n = version == 1 ? 17u : version == 2 ? 13u : version == 3 ? 12u : version == 4 ? 4u : 0u;
-  for (uint32_t i = 0; i < kPropsAppendixMax; ++i) a[i] = 0;
-  if (version == 1) a[0] = a[1] = a[2] = a[3] = 0xFF;
-  return n;
+__host__ __device__ inline uint32_t props_appendix_len(uint32_t version) {
+  return version == 1 ? 17u : version == 2 ? 13u : version == 3 ? 12u : version == 4 ? 4u : 0u;
+}
+// Byte k of the fields a stored `version` lacks: V1's account and container ids are -1, all else is 0.
+__host__ __device__ inline uint8_t props_appendix_byte(uint32_t version, uint32_t k) {
+  return version == 1 && k < 4 ? 0xFF : 0;
 }
 
 // What the transform must change in a stored payload of stored_len bytes to make its V5 bytes
@@ -209,20 +210,31 @@ __host__ __device__ inline PropsFix props_fix_of(const PropsFields& f, uint32_t 
 }
 
 __host__ __device__ inline uint32_t props_v5_len(const PropsFix& x) {
-  uint8_t a[kPropsAppendixMax];
-  return x.stored_len + (x.version ? props_appendix(x.version, a) : 0u);
+  return x.stored_len + props_appendix_len(x.version);
 }
 
-// Rewrite the stored payload at s (stored_len bytes already there) into its V5 bytes in place.
+// Byte j of the V5 payload, from the stored payload's byte j (`stored`; anything when j >= stored_len). The one
+// statement of the re-encoding: the transform's fix in place, the ingest and (with its own overlay, rekey.h)
+// the re-key write their payloads through it.
+__host__ __device__ inline uint8_t props_v5_byte(const PropsFix& x, uint32_t j, uint8_t stored) {
+  if (!x.version) return stored;
+  uint8_t b = j < x.stored_len ? stored : props_appendix_byte(x.version, j - x.stored_len);
+  if (j == 0) b = 0;
+  else if (j == 1) b = 5;
+  else if (j == kSerdePrivate) b = x.priv;
+  else if (x.enc_pos && j == x.enc_pos) b = x.enc;
+  return b;
+}
+
+// Rewrite the stored payload at s (stored_len bytes already there) into its V5 bytes in place: the bytes
+// props_v5_byte changes, and the appended ones.
 __host__ __device__ inline void props_apply_fix(uint8_t* s, const PropsFix& x) {
   if (!x.version) return;
-  s[0] = 0;
-  s[1] = 5;
-  s[kSerdePrivate] = x.priv;
-  if (x.enc_pos) s[x.enc_pos] = x.enc;
-  uint8_t a[kPropsAppendixMax];
-  const uint32_t n = props_appendix(x.version, a);
-  for (uint32_t i = 0; i < n; ++i) s[x.stored_len + i] = a[i];
+  s[0] = props_v5_byte(x, 0, s[0]);
+  s[1] = props_v5_byte(x, 1, s[1]);
+  s[kSerdePrivate] = props_v5_byte(x, kSerdePrivate, s[kSerdePrivate]);
+  if (x.enc_pos) s[x.enc_pos] = props_v5_byte(x, x.enc_pos, s[x.enc_pos]);
+  for (uint32_t j = x.stored_len, n = props_v5_len(x); j < n; ++j) s[j] = props_v5_byte(x, j, 0);
 }
 
 // Utils.addSecondsToEpochTime (Utils.java:1036-1041): Infinite_Time if either is, else

@@ -355,8 +355,9 @@ __device__ __forceinline__ FastPre transform_fast_pre(const FusedArgs& f, const 
   msg_fields(HeaderWordSrc{hw}, 3, &H);
   const int32_t(&rel)[kMsgSlots] = H.rel;
   bool ok = rel[2] == -1 && rel[1] >= 0 && rel[3] >= 0 && rel[4] >= 0 && (int64_t)rel[3] >= (int64_t)rel[1] + 10 &&
-            (uint64_t)rel[3] <= end && (uint64_t)rel[4] + 2 <= end;
-  if (ok) ok = ld_be16(p + rel[4]) == 3;
+            (uint64_t)rel[3] <= end && (uint64_t)rel[4] + 5 <= end;
+  // Blob_Format_V3 with isCompressed as the writer stores it (another byte reads as false and is written as 0)
+  if (ok) ok = ld_be16(p + rel[4]) == 3 && p[rel[4] + 4] <= 1;
   if (ok) {  // properties already canonical VERSION_5 bytes, every string ASCII (record_fields.h)
     const uint32_t stored = (uint32_t)(rel[3] - rel[1] - 10);
     PropsFields pf;

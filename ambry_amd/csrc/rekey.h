@@ -15,6 +15,7 @@
 
 #include "../../include/ambrycrc.h"
 #include "msg_header.h"
+#include "put_emit.h"
 #include "put_layout.h"
 
 namespace ambrycrc {
@@ -22,15 +23,17 @@ namespace ambrycrc {
 constexpr uint64_t kRekeyKeep = ~0ull;       // ambrycrc_rekey_desc::content_src: keep the stored content
 constexpr uint32_t kSerdeBlobSize = 19;      // offset of blobSize in the SerDe bytes (version, ttl, private, creationTime)
 
-// How a stored BlobPropertiesSerDe payload becomes the re-keyed VERSION_5 one, and what the write
+// How a stored BlobPropertiesSerDe payload becomes the re-keyed VERSION_5 one -- the transform's PropsFix
+// (record_fields.h) in its first 11 bytes, version 0 for a payload already canonical -- and what the write
 // step needs of the stored blob record (16 B a message in the workspace).
 struct RekeyFix {
   uint32_t stored_len;  // stored payload bytes
   uint32_t enc_pos;     // offset of the `encrypted` byte (stored version >= 3), else 0
-  uint32_t acct_pos;    // offset of the accountId short in the VERSION_5 bytes (containerId follows)
-  uint8_t version;      // stored SerDe version 1..5
+  uint8_t version;      // stored SerDe version 1..5, 0 = already canonical
   uint8_t priv, enc;    // canonical bytes (`== 1`)
   uint8_t blob_head;    // stored blob record head: 10, 12 or 13 B (Blob_Format_V1 / V2 / V3)
+  uint32_t acct_pos;    // offset of the accountId short in the VERSION_5 bytes (containerId follows)
+  __host__ __device__ PropsFix props() const { return PropsFix{stored_len, enc_pos, version, priv, enc, {0, 0, 0, 0, 0}}; }
 };
 static_assert(sizeof(RekeyFix) == 16, "RekeyFix");
 
@@ -42,17 +45,12 @@ __host__ __device__ inline bool rekey_desc_ok(const ambrycrc_rekey_desc& r, uint
   return r.content_len <= 0x7FFFFFFFull && r.content_src <= aux_len && r.content_len <= aux_len - r.content_src;
 }
 
-// Byte j of the re-keyed VERSION_5 payload, from the stored payload's byte j (`stored`; anything
-// when j >= stored_len): the transform's re-encoding (record_fields.h: SerDe version 5, canonical
-// private / encrypted bytes, the fields older versions lack appended as their defaults), then
-// blobSize when given and the new accountId / containerId.
+// Byte j of the re-keyed VERSION_5 payload, from the stored payload's byte j (`stored`; anything when j >=
+// stored_len): the transform's re-encoding (record_fields.h props_v5_byte), then blobSize when given and the
+// new accountId / containerId (over a stored V1's appended -1 ids too).
 __host__ __device__ inline uint8_t rekey_props_byte(const RekeyFix& x, const ambrycrc_rekey_desc& r, uint32_t j,
                                                     uint8_t stored) {
-  uint8_t b = j < x.stored_len ? stored : 0;  // appended fields: encrypted 0, null strings (int 0)
-  if (j == 0) b = 0;
-  else if (j == 1) b = 5;
-  else if (j == kSerdePrivate) b = x.priv;
-  else if (x.enc_pos && j == x.enc_pos) b = x.enc;
+  uint8_t b = props_v5_byte(x.props(), j, stored);
   if (r.props_blob_size >= 0 && j >= kSerdeBlobSize && j < kSerdeBlobSize + 8)
     b = (uint8_t)((uint64_t)r.props_blob_size >> (8 * (kSerdeBlobSize + 7 - j)));
   if (j >= x.acct_pos && j < x.acct_pos + 4) {
@@ -60,11 +58,6 @@ __host__ __device__ inline uint8_t rekey_props_byte(const RekeyFix& x, const amb
     b = (uint8_t)(ids >> (8 * (x.acct_pos + 3 - j)));
   }
   return b;
-}
-
-__host__ __device__ inline uint32_t rekey_props_len(const RekeyFix& x) {
-  uint8_t a[kPropsAppendixMax];
-  return x.stored_len + props_appendix(x.version, a);
 }
 
 // BlobIdTransformer.newMessage for the message at region + off, which the verify passed clean (its
@@ -77,7 +70,7 @@ __host__ __device__ inline uint32_t rekey_plan(const uint8_t* region, uint64_t o
                                                ambrycrc_put_desc* d, RekeyFix* x) {
   const uint8_t* p = region + off;
   const MsgHeader H = msg_header_of(p);
-  const int32_t enc = H.rel[0], bp = H.rel[1], upd = H.rel[2], um = H.rel[3], blob = H.rel[4];
+  const int32_t bp = H.rel[1], upd = H.rel[2], um = H.rel[3], blob = H.rel[4];
   if (upd != -1 || bp == -1 || um == -1 || blob == -1) return AMBRYCRC_MSG_NOT_PUT;  // "Only 'put' records are valid"
   // the deserializers' field reads against the header's spans (msg_header.h put_fields)
   const PutFields f = put_fields(p, H);
@@ -90,31 +83,18 @@ __host__ __device__ inline uint32_t rekey_plan(const uint8_t* region, uint64_t o
   const bool repl = r.content_src != kRekeyKeep;
   if (repl && type == 0) return AMBRYCRC_MSG_BAD_DESC;        // content is rewritten for a MetadataBlob only (:183)
   if (!repl && type == 1) return AMBRYCRC_MSG_NEEDS_CONTENT;  // ... and always for one (:185-247)
-  x->stored_len = (uint32_t)props_len;
-  x->version = (uint8_t)pf.version;
-  x->priv = pf.priv_raw == 1 ? 1 : 0;
-  x->enc = pf.enc_raw == 1 ? 1 : 0;
-  x->enc_pos = pf.version >= 3 ? pf.enc_pos : 0u;
+  const PropsFix fx = props_fix_of(pf, (uint32_t)props_len);
   // accountId: V1 stores none (the appendix starts with it), V2 ends with the two shorts, from V3 on
   // they sit right before the `encrypted` byte
-  x->acct_pos = pf.version == 1 ? (uint32_t)props_len : pf.version == 2 ? (uint32_t)props_len - 4 : pf.enc_pos - 4;
-  x->blob_head = (uint8_t)head;
-  __builtin_memset(d, 0, sizeof *d);
-  const bool keep_enc = enc != -1 && header_version >= 2;
+  const uint32_t acct = pf.version == 1 ? (uint32_t)props_len : pf.version == 2 ? (uint32_t)props_len - 4 : pf.enc_pos - 4;
+  *x = RekeyFix{fx.stored_len, fx.enc_pos, fx.version, fx.priv, fx.enc, (uint8_t)head, acct};
+  *d = put_desc_of_stored(off, H, f, header_version, have_life ? life_version : H.life, props_v5_len(fx));
   d->key_src = r.key_src;
   d->key_len = r.key_len;
-  d->enckey_src = keep_enc ? off + enc + 6 : 0;
-  d->enckey_len = keep_enc ? (int32_t)f.enc_len : -1;
-  d->props_src = off + bp + 2;
-  d->props_len = rekey_props_len(*x);
-  d->usermeta_src = off + um + 6;
-  d->usermeta_len = f.um_len;
-  d->blob_src = repl ? r.content_src : off + blob + head;
-  d->blob_len = repl ? r.content_len : f.size;
-  d->life_version = (int16_t)(have_life ? life_version : H.life);
-  d->blob_type = (int16_t)type;
-  d->compressed = (uint8_t)f.comp;
-  d->header_version = (uint8_t)header_version;
+  if (repl) {
+    d->blob_src = r.content_src;
+    d->blob_len = r.content_len;
+  }
   PutLayout L;
   if (!put_layout(*d, L)) {  // a relative offset past a Java int
     d->header_version = 0;

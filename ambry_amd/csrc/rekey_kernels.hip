@@ -26,6 +26,7 @@
 #include "crc32_kernels.h"
 #include "crc32_layout.h"
 #include "crc_img.h"
+#include "put_emit.h"
 #include "put_layout.h"
 #include "record_fields.h"
 #include "rekey.h"
@@ -69,16 +70,14 @@ __global__ __launch_bounds__(256) void rekey_plan_kernel(RekeyArgs a) {
   }
 }
 
-// One CRC step over byte b through the LDS byte table (t[0..255] = T0, stage_slice_tables).
-__device__ __forceinline__ uint32_t crc_step(const uint32_t* __restrict__ t, uint32_t c, uint32_t b) {
-  return t[(c ^ b) & 0xffu] ^ (c >> 8);
-}
-
-__global__ __launch_bounds__(256) void rekey_write_kernel(RekeyArgs a) {
+// Five waves a SIMD, as before the writers were shared (put_emit.h): left to itself the allocator takes two or
+// three VGPRs past the 96 that allow them.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void rekey_write_kernel(RekeyArgs a) {
   __shared__ uint32_t tbl[1024];
   stage_slice_tables(tbl, a.img);
   __syncthreads();
   const uint64_t m = a.m;
+  const auto crc16 = [&](const uint8_t(&b)[16], uint32_t n) { return crc_regs_lds(tbl, 0u, b, n); };
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (uint64_t)gridDim.x * blockDim.x) {
     const ambrycrc_put_desc d = a.desc[i];
     uint64_t src[kRekeySlots] = {0, 0, 0, 0}, dst[kRekeySlots] = {0, 0, 0, 0}, len[kRekeySlots] = {0, 0, 0, 0};
@@ -88,75 +87,20 @@ __global__ __launch_bounds__(256) void rekey_write_kernel(RekeyArgs a) {
       const RekeyFix x = a.fix[i];
       const bool repl = r.content_src != kRekeyKeep;
       uint8_t* msg = a.out + d.out_off;
-      {  // header and its CRC, from the bytes in registers
-        uint8_t h[32];
-        const uint32_t hn = put_header_bytes(d, L, h);
-        if (hn == 32) __builtin_memcpy(msg, h, 32);
-        else if (hn == 30) __builtin_memcpy(msg, h, 30);
-        else __builtin_memcpy(msg, h, 26);
-        put_be64(msg + hn, (uint64_t)crc_regs_lds(tbl, 0u, h, hn));
-      }
-      {  // BlobProperties_Format_V1: version 1, the re-keyed VERSION_5 bytes, their CRC -- 8 B at a time
-        const uint8_t* ps = a.region + d.props_src;
-        uint8_t* pd = msg + L.bp_rel;
-        put_be16(pd, 1u);
-        pd += 2;
-        uint32_t c = crc_step(tbl, crc_step(tbl, 0xFFFFFFFFu, 0u), 1u);
-        const uint32_t n = d.props_len;
-        for (uint32_t j0 = 0; j0 < n; j0 += 8) {
-          uint64_t w = 0;
-          if (j0 + 8 <= x.stored_len) {
-            __builtin_memcpy(&w, ps + j0, 8);
-          } else {
-#pragma unroll
-            for (uint32_t b = 0; b < 8; ++b)
-              if (j0 + b < x.stored_len) w |= (uint64_t)ps[j0 + b] << (8 * b);
-          }
-          uint64_t o = 0;
-#pragma unroll
-          for (uint32_t b = 0; b < 8; ++b) {
-            if (j0 + b < n) {
-              const uint32_t v = rekey_props_byte(x, r, j0 + b, (uint8_t)(w >> (8 * b)));
-              o |= (uint64_t)v << (8 * b);
-              c = crc_step(tbl, c, v);
-            }
-          }
-          if (j0 + 8 <= n) {
-            __builtin_memcpy(pd + j0, &o, 8);
-          } else {
-#pragma unroll
-            for (uint32_t b = 0; b < 8; ++b)
-              if (j0 + b < n) pd[j0 + b] = (uint8_t)(o >> (8 * b));
-          }
-        }
-        put_be64(pd + n, (uint64_t)~c);
-      }
-      {  // Blob_Format_V3 head and the record's CRC
+      put_emit_header<true>(tbl, d, L, msg);
+      // BlobProperties_Format_V1: the re-keyed VERSION_5 bytes
+      put_emit_props(tbl, a.region + d.props_src, x.stored_len, msg + L.bp_rel, d.props_len,
+                     [&](uint32_t j, uint8_t stored) { return rekey_props_byte(x, r, j, stored); });
+      if (repl) {  // Blob_Format_V3 over the content hashed from aux
+        put_emit_record<4>(tbl, a.img, d, L, msg, &a.ccrc[i]);
+      } else {  // ... or over the stored record's content, whose record verified: its CRC moved to the new head
         uint8_t h3[16];
         put_prefix_bytes(d, 4, h3);
         uint8_t* bd = msg + L.blob_rel;
         __builtin_memcpy(bd, h3, 13);
-        uint32_t crc;
-        if (repl) {
-          // crc(head || content) = crc(head) x^(8|content|) + crc(content), the content hashed from aux
-          crc = mul_xpow8_img(a.img, crc_regs_lds(tbl, 0u, h3, 13u), d.blob_len) ^ a.ccrc[i];
-        } else {
-          // the stored record verified: its CRC is the low word of its trailer; a head that changes
-          // (V1 / V2 -> V3, or a non-canonical isCompressed byte) moves it by
-          // (crc(old head) ^ crc(new head)) x^(8|content|), with no pass over the content
-          const uint8_t* sb = a.region + d.blob_src;
-          crc = ld_be32(sb + d.blob_len + 4);
-          const uint8_t* sh = sb - x.blob_head;
-          if (x.blob_head != 13 || sh[4] != h3[4]) {
-            uint8_t oh[16];
-#pragma unroll
-            for (uint32_t b = 0; b < 16; ++b) oh[b] = b < x.blob_head ? sh[b] : 0;
-            const uint32_t ca = crc_regs_lds(tbl, 0u, oh, (uint32_t)x.blob_head);
-            const uint32_t cb = crc_regs_lds(tbl, 0u, h3, 13u);
-            crc ^= mul_xpow8_img(a.img, ca ^ cb, d.blob_len);
-          }
-        }
-        put_be64(bd + 13 + d.blob_len, (uint64_t)crc);
+        const uint8_t* sb = a.region + d.blob_src;
+        put_be64(bd + 13 + d.blob_len, (uint64_t)blob_crc_moved(crc16, a.img, sb - x.blob_head, x.blob_head, h3,
+                                                                ld_be32(sb + d.blob_len + 4), d.blob_len));
       }
       // the bodies: key from aux; the encryption-key and user-metadata records whole (prefix, body
       // and verified trailer are the output's bytes); the content from the region or aux
@@ -175,13 +119,7 @@ __global__ __launch_bounds__(256) void rekey_write_kernel(RekeyArgs a) {
       dst[3] = d.out_off + (uint64_t)L.blob_rel + 13;
       len[3] = d.blob_len;
     }
-#pragma unroll
-    for (uint32_t k = 0; k < kRekeySlots; ++k) {
-      a.cp_src[k * m + i] = src[k];
-      a.cp_dst[k * m + i] = dst[k];
-      a.cp_len[k * m + i] = len[k];
-      a.cp_cost[k * m + i] = len[k] ? len[k] + kCopyJobCost : 0;
-    }
+    store_copy_jobs(a.cp_src, a.cp_dst, a.cp_len, a.cp_cost, m, i, src, dst, len);
   }
 }
 

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void send_jobs_kernel(SendArgs a) {
       const uint64_t gl = at != kSendNowhere ? a.g_len[i] : 0;
       a.g_dst[i] = gl ? at : 0;
       a.g_len[i] = gl;
-      a.g_cost[i] = gl ? gl + kCopyJobCost : 0;
+      a.g_cost[i] = copy_job_cost(gl);
     }
   }
 }

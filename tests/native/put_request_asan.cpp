@@ -99,7 +99,7 @@ static uint32_t parse_exact(const uint8_t* src, size_t n, ambrycrc_put_request_r
         const PropsFix x = ingest_props_fix(p);
         uint32_t acc = 0;
         for (uint32_t j = 0; j < d.props_len; ++j)
-          acc += ingest_props_byte(x, j, j < x.stored_len ? wire[d.props_src + j] : 0);
+          acc += props_v5_byte(x, j, j < x.stored_len ? wire[d.props_src + j] : 0);
         if (info.size != L.length || acc == 0) ++g_bad, fprintf(stderr, "info / properties\n");
       } else if (expect_clean) {
         ++g_bad, fprintf(stderr, "a clean frame got verdict %x\n", vs);
