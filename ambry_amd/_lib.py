@@ -10,40 +10,13 @@ import ctypes
 import os
 import threading
 
+from .abi import (AMBRYCRC_ECOMM, AMBRYCRC_EHIP, AMBRYCRC_EINVAL, AMBRYCRC_ENODEV, AMBRYCRC_ENOINIT,  # noqa: F401
+                  AMBRYCRC_ENOMEM, AMBRYCRC_EPROBE, AMBRYCRC_OK, UNIQUE_ID_BYTES, PutDesc, Shard)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # AMBRYCRC_LIBRARY names another build of the same library (A/B timing of two kernel builds on
 # one box, tools/ab_cases.sh); default: the in-tree build.
 LIB_PATH = os.environ.get("AMBRYCRC_LIBRARY") or os.path.join(_HERE, "libambrycrc.so")
-
-AMBRYCRC_OK = 0
-AMBRYCRC_EINVAL = -1
-AMBRYCRC_EHIP = -2
-AMBRYCRC_ENOMEM = -3
-AMBRYCRC_ENOINIT = -4
-AMBRYCRC_ENODEV = -5
-AMBRYCRC_ECOMM = -6
-AMBRYCRC_EPROBE = -7
-UNIQUE_ID_BYTES = 128
-
-
-class Shard(ctypes.Structure):
-    """struct ambrycrc_shard (include/ambrycrc.h): one GPU's part of a multi-GPU batch."""
-    _fields_ = [("device", ctypes.c_int), ("d_base", ctypes.c_void_p), ("d_off", ctypes.c_void_p),
-                ("d_len", ctypes.c_void_p), ("d_crc_in", ctypes.c_void_p), ("n", ctypes.c_size_t),
-                ("d_gathered", ctypes.c_void_p), ("stream", ctypes.c_void_p)]
-
-
-class PutDesc(ctypes.Structure):
-    """struct ambrycrc_put_desc (include/ambrycrc.h): one PUT message to serialize (80 bytes)."""
-    _fields_ = [("out_off", ctypes.c_uint64), ("key_src", ctypes.c_uint64), ("enckey_src", ctypes.c_uint64),
-                ("props_src", ctypes.c_uint64), ("usermeta_src", ctypes.c_uint64), ("blob_src", ctypes.c_uint64),
-                ("blob_len", ctypes.c_uint64), ("key_len", ctypes.c_uint32), ("enckey_len", ctypes.c_int32),
-                ("props_len", ctypes.c_uint32), ("usermeta_len", ctypes.c_uint32), ("life_version", ctypes.c_int16),
-                ("blob_type", ctypes.c_int16), ("compressed", ctypes.c_uint8), ("header_version", ctypes.c_uint8),
-                ("reserved", ctypes.c_uint8 * 2)]
-
-
-assert ctypes.sizeof(PutDesc) == 80
 
 # (name, restype, argtypes) for every symbol include/ambrycrc.h declares.
 _u8p = ctypes.c_void_p

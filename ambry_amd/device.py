@@ -10,73 +10,40 @@ from __future__ import annotations
 
 import ctypes
 
-from ._lib import UNIQUE_ID_BYTES, Shard, check, lib
+import numpy as np
 
-
-def _torch():
-    import torch  # deferred: CPU-only tests import this module without a GPU
-
-    return torch
-
-
-def _stream_handle(stream=None) -> int:
-    torch = _torch()
-    s = stream if stream is not None else torch.cuda.current_stream()
-    return s.cuda_stream
-
-
-def _ptr(t) -> ctypes.c_void_p | None:
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+from ._args import dev_tensor, host_buffer, message_batch, ptr, stream_handle, workspace as _workspace
+from ._args import torch as _torch
+from ._lib import check, lib
+from .abi import (HARD_DELETE_INFO, MESSAGE_INFO, MSG_BAD_INFO, NO_MESSAGE, RECOVER_RESULT,  # noqa: F401
+                  UNIQUE_ID_BYTES, Shard)
 
 
 def init(device: int = 0) -> None:
     check(lib().ambrycrc_init(device), f"ambrycrc_init({device})")
 
 
-def _check_batch(base, off, length, n):
+def _check_batch(base, off, length, crc=()):
+    """n after checking a CRC batch: base uint8, off and len int64[n], the (name, tensor) pairs of crc int32 or
+    uint32[n] or None, all contiguous CUDA tensors on base's device."""
     torch = _torch()
-    if base.dtype != torch.uint8 or not base.is_cuda:
-        raise TypeError("base must be a uint8 CUDA tensor")
-    for name, t in (("off", off), ("len", length)):
-        if t.dtype != torch.int64 or not t.is_cuda or t.numel() != n or not t.is_contiguous():
-            raise TypeError(f"{name} must be a contiguous int64 CUDA tensor of {n} elements")
-        if t.device != base.device:
-            raise TypeError(f"{name} must be on {base.device}")
-
-
-def _check_u32(name, t, n, device):
-    """crc_in / out / expected: a contiguous int32 or uint32 CUDA tensor of n elements on `device`."""
-    torch = _torch()
-    if t is None:
-        return
-    if t.dtype not in (torch.int32, torch.uint32) or not t.is_cuda or t.numel() != n or not t.is_contiguous():
-        raise TypeError(f"{name} must be a contiguous int32/uint32 CUDA tensor of {n} elements")
-    if t.device != device:
-        raise TypeError(f"{name} must be on {device}")
-
-
-def _workspace(workspace, device):
-    """(pointer, byte size) of a caller workspace (any dtype: its byte size is what counts)."""
-    if workspace is None:
-        return None, 0
-    if not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != device:
-        raise TypeError(f"workspace must be a contiguous CUDA tensor on {device}")
-    return _ptr(workspace), workspace.numel() * workspace.element_size()
+    dev_tensor("base", base, torch.uint8)
+    n = dev_tensor("off", off, torch.int64, like=base).numel()
+    dev_tensor("len", length, torch.int64, n, base)
+    for name, t in crc:
+        dev_tensor(name, t, (torch.int32, torch.uint32), n, base, optional=True)
+    return n
 
 
 def crc32_batch(base, off, length, crc_in=None, out=None, workspace=None, stream=None):
     """out[i] = crc32(crc_in[i] or 0, base[off[i]:off[i]+len[i]]) for every chunk i (on the GPU).
     out may be crc_in itself (an in-place continuation)."""
-    torch = _torch()
-    n = off.numel()
-    _check_batch(base, off, length, n)
-    _check_u32("crc_in", crc_in, n, base.device)
-    _check_u32("out", out, n, base.device)
+    n = _check_batch(base, off, length, (("crc_in", crc_in), ("out", out)))
     if out is None:
-        out = torch.empty(n, dtype=torch.int32, device=base.device)
-    ws, ws_bytes = _workspace(workspace, base.device)
-    check(lib().ambrycrc_batch_dev(_ptr(base), _ptr(off), _ptr(length), _ptr(crc_in), _ptr(out), n, ws, ws_bytes,
-                                   ctypes.c_void_p(_stream_handle(stream))), "ambrycrc_batch_dev")
+        out = _torch().empty(n, dtype=_torch().int32, device=base.device)
+    ws, ws_bytes = _workspace(workspace, base)
+    check(lib().ambrycrc_batch_dev(ptr(base), ptr(off), ptr(length), ptr(crc_in), ptr(out), n, ws, ws_bytes,
+                                   stream_handle(stream)), "ambrycrc_batch_dev")
     return out
 
 
@@ -85,33 +52,26 @@ def crc32_verify(base, off, length, expected, crc_in=None, out=None, stream=None
     """Returns (crc int32[n], mismatch uint8[n], mismatch_count int32[1] or None) computed on the GPU.
     mismatch: optional preallocated uint8[n]; count=False skips the counter (and its zeroing)."""
     torch = _torch()
-    n = off.numel()
-    _check_batch(base, off, length, n)
-    for name, t in (("crc_in", crc_in), ("out", out), ("expected", expected)):
-        _check_u32(name, t, n, base.device)
+    n = _check_batch(base, off, length, (("crc_in", crc_in), ("out", out), ("expected", expected)))
     if expected is None:
         raise TypeError("expected is required")
-    if mismatch is not None and (mismatch.dtype != torch.uint8 or not mismatch.is_cuda or mismatch.numel() != n
-                                 or not mismatch.is_contiguous() or mismatch.device != base.device):
-        raise TypeError(f"mismatch must be a contiguous uint8 CUDA tensor of {n} elements on {base.device}")
+    dev_tensor("mismatch", mismatch, torch.uint8, n, base, optional=True)
     if out is None:
         out = torch.empty(n, dtype=torch.int32, device=base.device)
     if mismatch is None:
         mismatch = torch.empty(n, dtype=torch.uint8, device=base.device)
     count = torch.zeros(1, dtype=torch.int32, device=base.device) if count else None
-    check(lib().ambrycrc_verify_dev(_ptr(base), _ptr(off), _ptr(length), _ptr(crc_in), _ptr(expected), _ptr(out),
-                                    _ptr(mismatch), _ptr(count), n, None, 0,
-                                    ctypes.c_void_p(_stream_handle(stream))), "ambrycrc_verify_dev")
+    check(lib().ambrycrc_verify_dev(ptr(base), ptr(off), ptr(length), ptr(crc_in), ptr(expected), ptr(out),
+                                    ptr(mismatch), ptr(count), n, None, 0, stream_handle(stream)),
+          "ambrycrc_verify_dev")
     return out, mismatch, count
 
 
 def fill_random(buf, seed: int, stream_off: int = 0, stream=None) -> None:
     """Deterministic splitmix64 bytes (same stream as oracle_fill_splitmix)."""
-    torch = _torch()
-    if buf.dtype != torch.uint8 or not buf.is_cuda or not buf.is_contiguous():
-        raise TypeError("buf must be a contiguous uint8 CUDA tensor")
-    check(lib().ambrycrc_fill_random_dev(_ptr(buf), buf.numel(), seed & (2**64 - 1), stream_off,
-                                         ctypes.c_void_p(_stream_handle(stream))), "ambrycrc_fill_random_dev")
+    dev_tensor("buf", buf, _torch().uint8)
+    check(lib().ambrycrc_fill_random_dev(ptr(buf), buf.numel(), seed & (2**64 - 1), stream_off,
+                                         stream_handle(stream)), "ambrycrc_fill_random_dev")
 
 
 def _host_chunks(chunks, crc_in):
@@ -299,56 +259,13 @@ def verify_messages(region, msg_off, stream=None, want_end: bool = True):
     Returns (status int32[m] of AMBRYCRC_MSG_* bits, msg_end int64[m] or None).
     """
     torch = _torch()
-    if region.dtype != torch.uint8 or not region.is_cuda:
-        raise TypeError("region must be a uint8 CUDA tensor")
-    if msg_off.dtype != torch.int64 or not msg_off.is_cuda or not msg_off.is_contiguous() or \
-            msg_off.device != region.device:
-        raise TypeError(f"msg_off must be a contiguous int64 CUDA tensor on {region.device}")
-    m = msg_off.numel()
+    m = message_batch(region, msg_off)
     status = torch.empty(m, dtype=torch.int32, device=region.device)
     end = torch.empty(m, dtype=torch.int64, device=region.device) if want_end else None
-    check(lib().ambrycrc_verify_messages_dev(_ptr(region), region.numel(), _ptr(msg_off), m, _ptr(status),
-                                             _ptr(end), None, 0, ctypes.c_void_p(_stream_handle(stream))),
+    check(lib().ambrycrc_verify_messages_dev(ptr(region), region.numel(), ptr(msg_off), m, ptr(status),
+                                             ptr(end), None, 0, stream_handle(stream)),
           "ambrycrc_verify_messages_dev")
     return status, end
-
-
-def _hard_delete_info_dtype():
-    """struct ambrycrc_hard_delete_info (include/ambrycrc.h) as a numpy structured dtype: 32 bytes, no padding.
-    Built on first use and kept as HARD_DELETE_INFO: numpy stays a deferred import in this module, as torch is."""
-    if "HARD_DELETE_INFO" not in globals():
-        import numpy as np
-
-        dt = np.dtype([("blob_size", "<u8"), ("size", "<u8"), ("start", "<u4"), ("usermeta_size", "<u4"),
-                       ("header_version", "<i2"), ("usermeta_version", "<i2"), ("blob_version", "<i2"),
-                       ("blob_type", "<i2")])
-        assert dt.itemsize == 32
-        globals()["HARD_DELETE_INFO"] = dt
-    return globals()["HARD_DELETE_INFO"]
-
-
-def _recover_dtypes():
-    """struct ambrycrc_message_info (48 bytes) and struct ambrycrc_recover_result (32 bytes) of include/ambrycrc.h
-    as numpy structured dtypes, built on first use and kept as MESSAGE_INFO and RECOVER_RESULT."""
-    if "MESSAGE_INFO" not in globals():
-        import numpy as np
-
-        info = np.dtype([("msg_off", "<u8"), ("size", "<u8"), ("expires_at_ms", "<i8"), ("operation_time_ms", "<i8"),
-                         ("key_rel", "<u4"), ("key_len", "<u4"), ("account_id", "<i2"), ("container_id", "<i2"),
-                         ("life_version", "<i2"), ("flags", "u1"), ("header_version", "u1")])
-        res = np.dtype([("chained", "<u8"), ("recovered", "<u8"), ("end_off", "<u8"), ("end_status", "<u4"),
-                        ("more", "<u4")])
-        assert info.itemsize == 48 and res.itemsize == 32
-        globals()["MESSAGE_INFO"], globals()["RECOVER_RESULT"] = info, res
-    return globals()["MESSAGE_INFO"], globals()["RECOVER_RESULT"]
-
-
-def __getattr__(name):
-    if name == "HARD_DELETE_INFO":
-        return _hard_delete_info_dtype()
-    if name in ("MESSAGE_INFO", "RECOVER_RESULT"):
-        return _recover_dtypes()[name == "RECOVER_RESULT"]
-    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def hard_delete_workspace_bytes(m: int) -> int:
@@ -366,22 +283,14 @@ def hard_delete_messages(region, msg_off, recovery=None, plan_only: bool = False
     Returns (status int32[m] of AMBRYCRC_MSG_* bits, 0 = hard-deleted; info uint8[m, 32] CUDA tensor:
     rows of HARD_DELETE_INFO, zero for a refused message)."""
     torch = _torch()
-    if region.dtype != torch.uint8 or not region.is_cuda or not region.is_contiguous():
-        raise TypeError("region must be a contiguous uint8 CUDA tensor")
-    if msg_off.dtype != torch.int64 or not msg_off.is_cuda or not msg_off.is_contiguous() or \
-            msg_off.device != region.device:
-        raise TypeError(f"msg_off must be a contiguous int64 CUDA tensor on {region.device}")
-    m = msg_off.numel()
-    if recovery is not None and (recovery.dtype != torch.uint8 or not recovery.is_cuda or
-                                 not recovery.is_contiguous() or recovery.numel() != 32 * m or
-                                 recovery.device != region.device):
-        raise TypeError(f"recovery must be a contiguous uint8[{m}, 32] CUDA tensor on {region.device}")
+    m = message_batch(region, msg_off)
+    dev_tensor("recovery", recovery, torch.uint8, m, region, optional=True, unit=32)
     status = torch.empty(m, dtype=torch.int32, device=region.device)
     info = torch.empty((m, 32), dtype=torch.uint8, device=region.device)
-    ws, ws_bytes = _workspace(workspace, region.device)
-    check(lib().ambrycrc_hard_delete_messages_dev(_ptr(region), region.numel(), _ptr(msg_off), m, _ptr(recovery),
-                                                  1 if plan_only else 0, _ptr(status), _ptr(info), ws, ws_bytes,
-                                                  ctypes.c_void_p(_stream_handle(stream))),
+    ws, ws_bytes = _workspace(workspace, region)
+    check(lib().ambrycrc_hard_delete_messages_dev(ptr(region), region.numel(), ptr(msg_off), m, ptr(recovery),
+                                                  1 if plan_only else 0, ptr(status), ptr(info), ws, ws_bytes,
+                                                  stream_handle(stream)),
           "ambrycrc_hard_delete_messages_dev")
     return status, info
 
@@ -390,23 +299,15 @@ def hard_delete_message_cpu(region, off: int, recovery=None, plan_only: bool = F
     """ambrycrc_hard_delete_message_cpu: the same for the one message at `off` of a region in host memory,
     in place (a writable numpy uint8 array or bytearray). recovery: a HARD_DELETE_INFO record (or None).
     Returns (status, info: a HARD_DELETE_INFO record, zero when refused)."""
-    import numpy as np
-
-    dtype = _hard_delete_info_dtype()
-    arr = np.frombuffer(region, dtype=np.uint8) if isinstance(region, (bytearray, memoryview)) else region
-    if not isinstance(arr, np.ndarray) or arr.dtype != np.uint8 or not arr.flags.c_contiguous or \
-            not arr.flags.writeable:
-        raise TypeError("region must be a writable contiguous uint8 array or a bytearray")
+    _keep, base, nbytes = host_buffer("region", region, writable=True)
     rec = None
     if recovery is not None:
-        rec = np.zeros(1, dtype=dtype)
+        rec = np.zeros(1, dtype=HARD_DELETE_INFO)
         rec[0] = recovery
-    info = np.zeros(1, dtype=dtype)
+    info = np.zeros(1, dtype=HARD_DELETE_INFO)
     status = ctypes.c_uint32()
-    check(lib().ambrycrc_hard_delete_message_cpu(ctypes.c_void_p(arr.ctypes.data if arr.nbytes else 0), arr.nbytes,
-                                                 off, None if rec is None else ctypes.c_void_p(rec.ctypes.data),
-                                                 1 if plan_only else 0, ctypes.byref(status),
-                                                 ctypes.c_void_p(info.ctypes.data)),
+    check(lib().ambrycrc_hard_delete_message_cpu(base, nbytes, off, None if rec is None else rec.ctypes.data,
+                                                 1 if plan_only else 0, ctypes.byref(status), info.ctypes.data),
           "ambrycrc_hard_delete_message_cpu")
     return status.value, info[0]
 
@@ -415,12 +316,11 @@ def verify_trailed(base, off, length, stream=None):
     """CRC-trailered items on the GPU: item i = base[off[i]:off[i]+len[i]] ends in the big-endian
     8-B CRC of the bytes before it. Returns (mismatch uint8[n], count int32[1])."""
     torch = _torch()
-    n = off.numel()
-    _check_batch(base, off, length, n)
+    n = _check_batch(base, off, length)
     mismatch = torch.empty(n, dtype=torch.uint8, device=base.device)
     count = torch.zeros(1, dtype=torch.int32, device=base.device)
-    check(lib().ambrycrc_verify_trailed_dev(_ptr(base), _ptr(off), _ptr(length), _ptr(mismatch), _ptr(count), n,
-                                            None, 0, ctypes.c_void_p(_stream_handle(stream))),
+    check(lib().ambrycrc_verify_trailed_dev(ptr(base), ptr(off), ptr(length), ptr(mismatch), ptr(count), n,
+                                            None, 0, stream_handle(stream)),
           "ambrycrc_verify_trailed_dev")
     return mismatch, count
 
@@ -428,13 +328,10 @@ def verify_trailed(base, off, length, stream=None):
 def verify_trailed_host(buffers, device: int = 0, pinned: bool = False):
     """The same over host buffers (bytes-likes, e.g. whole files): returns a list of bools, True =
     the trailer does not match (IndexSegment.checkDataIntegrityInByteBufferWithCRC is False)."""
-    import numpy as np
-
-    arrs = [np.frombuffer(b, dtype=np.uint8) if isinstance(b, (bytes, bytearray, memoryview)) else
-            np.ascontiguousarray(b, dtype=np.uint8) for b in buffers]
-    n = len(arrs)
-    ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data if a.nbytes else None for a in arrs])
-    lens = (ctypes.c_uint64 * n)(*[a.nbytes for a in arrs])
+    bufs = [host_buffer("buffers[%d]" % i, b) for i, b in enumerate(buffers)]
+    n = len(bufs)
+    ptrs = (ctypes.c_void_p * n)(*[b[1] or None for b in bufs])
+    lens = (ctypes.c_uint64 * n)(*[b[2] for b in bufs])
     mism = (ctypes.c_uint8 * n)()
     check(lib().ambrycrc_verify_trailed_host(ptrs, lens, mism, n, device, 1 if pinned else 0),
           "ambrycrc_verify_trailed_host")
@@ -445,43 +342,28 @@ def verify_messages_host(region, msg_off, device: int = 0, pinned: bool = False)
     """verify_messages for a region in host memory (bytes, numpy uint8, or a CPU uint8 tensor;
     pinned=True for a hipHostMalloc'd / pin_memory() buffer). Returns (status uint32[m],
     msg_end uint64[m]) as numpy arrays."""
-    import numpy as np
-
-    if hasattr(region, "data_ptr"):  # torch CPU tensor
-        ptr, nbytes, keep = region.data_ptr(), region.numel(), region
-    else:
-        arr = np.frombuffer(region, dtype=np.uint8) if isinstance(region, (bytes, bytearray)) else \
-            np.ascontiguousarray(region, dtype=np.uint8)
-        ptr, nbytes, keep = arr.ctypes.data, arr.nbytes, arr
+    _keep, base, nbytes = host_buffer("region", region)
     offs = np.ascontiguousarray(np.asarray(msg_off, dtype=np.uint64))
     m = len(offs)
     status = np.zeros(m, dtype=np.uint32)
     end = np.zeros(m, dtype=np.uint64)
     check(lib().ambrycrc_verify_messages_host(
-        ctypes.c_void_p(ptr), nbytes, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), m,
+        base, nbytes, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), m,
         status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), end.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
         device, 1 if pinned else 0), "ambrycrc_verify_messages_host")
-    del keep
     return status, end
 
 
 def chain_messages_host(region: bytes, start: int = 0, max_messages: int = 1 << 20):
     """Offsets of consecutive messages from `start` in a host buffer (BlobStoreRecovery's hop)."""
-    import numpy as np
-
-    arr = np.frombuffer(region, dtype=np.uint8) if isinstance(region, (bytes, bytearray, memoryview)) else \
-        np.ascontiguousarray(region, dtype=np.uint8)  # no copy for bytes, mmaps and uint8 arrays
+    _keep, base, nbytes = host_buffer("region", region)  # no copy for bytes, mmaps and uint8 arrays
     offs = np.zeros(max_messages, dtype=np.uint64)
-    n = lib().ambrycrc_chain_messages_host(ctypes.c_void_p(arr.ctypes.data if arr.nbytes else 0), arr.nbytes, start,
-                                           offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), max_messages)
+    n = lib().ambrycrc_chain_messages_host(base, nbytes, start, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                           max_messages)
     return [int(x) for x in offs[:n]]
 
 
 # ------------------------------------------------ log-region recovery on the device (DESIGN.md §16)
-
-MSG_BAD_INFO = 1 << 16    # AMBRYCRC_MSG_BAD_INFO: an operation time below -1 (MessageInfo's constructor throws)
-NO_MESSAGE = (1 << 64) - 1  # d_msg_off of a slot past the chain (UINT64_MAX; -1 in the int64 tensor)
-
 
 def chain_workspace_bytes(region_len: int, max_messages: int) -> int:
     """Bytes of caller workspace ambrycrc_chain_messages_dev needs."""
@@ -493,12 +375,6 @@ def recover_workspace_bytes(region_len: int, max_messages: int) -> int:
     return lib().ambrycrc_recover_workspace_bytes(region_len, max_messages)
 
 
-def _check_region(region):
-    torch = _torch()
-    if region.dtype != torch.uint8 or not region.is_cuda or not region.is_contiguous():
-        raise TypeError("region must be a contiguous uint8 CUDA tensor")
-
-
 def chain_messages(region, start: int = 0, max_messages: int = 1 << 20, stream=None, workspace=None, out=None):
     """The message chain of a log region in HBM, found on the GPU (ambrycrc_chain_messages_dev): no host
     synchronisation. out: (msg_off, result) of an earlier call, to write into (a captured graph's outputs).
@@ -506,13 +382,13 @@ def chain_messages(region, start: int = 0, max_messages: int = 1 << 20, stream=N
     Returns (msg_off int64[max_messages] CUDA tensor: the starts in log order, then -1 (UINT64_MAX);
     result uint8[32] CUDA tensor: one RECOVER_RESULT record -- recover_result(result) reads it)."""
     torch = _torch()
-    _check_region(region)
+    dev_tensor("region", region, torch.uint8)
     msg_off, result = out if out is not None else (
         torch.empty(max_messages, dtype=torch.int64, device=region.device),
         torch.empty(32, dtype=torch.uint8, device=region.device))
-    ws, ws_bytes = _workspace(workspace, region.device)
-    check(lib().ambrycrc_chain_messages_dev(_ptr(region), region.numel(), start, max_messages, _ptr(msg_off),
-                                            _ptr(result), ws, ws_bytes, ctypes.c_void_p(_stream_handle(stream))),
+    ws, ws_bytes = _workspace(workspace, region)
+    check(lib().ambrycrc_chain_messages_dev(ptr(region), region.numel(), start, max_messages, ptr(msg_off),
+                                            ptr(result), ws, ws_bytes, stream_handle(stream)),
           "ambrycrc_chain_messages_dev")
     return msg_off, result
 
@@ -525,45 +401,37 @@ def recover_messages(region, start: int = 0, max_messages: int = 1 << 20, stream
     Returns (msg_off int64[max_messages], info uint8[max_messages, 48]: rows of MESSAGE_INFO, zero unless the
     status is 0; status int32[max_messages]; result uint8[32]: one RECOVER_RESULT record), CUDA tensors."""
     torch = _torch()
-    _check_region(region)
+    dev_tensor("region", region, torch.uint8)
     msg_off, info, status, result = out if out is not None else (
         torch.empty(max_messages, dtype=torch.int64, device=region.device),
         torch.empty((max_messages, 48), dtype=torch.uint8, device=region.device),
         torch.empty(max_messages, dtype=torch.int32, device=region.device),
         torch.empty(32, dtype=torch.uint8, device=region.device))
-    ws, ws_bytes = _workspace(workspace, region.device)
-    check(lib().ambrycrc_recover_messages_dev(_ptr(region), region.numel(), start, max_messages, _ptr(msg_off),
-                                              _ptr(info), _ptr(status), _ptr(result), ws, ws_bytes,
-                                              ctypes.c_void_p(_stream_handle(stream))),
+    ws, ws_bytes = _workspace(workspace, region)
+    check(lib().ambrycrc_recover_messages_dev(ptr(region), region.numel(), start, max_messages, ptr(msg_off),
+                                              ptr(info), ptr(status), ptr(result), ws, ws_bytes,
+                                              stream_handle(stream)),
           "ambrycrc_recover_messages_dev")
     return msg_off, info, status, result
 
 
 def recover_result(result):
     """The RECOVER_RESULT record of a result tensor (copies it to the host: synchronises)."""
-    import numpy as np
-
-    return np.frombuffer(result.cpu().numpy().tobytes(), dtype=_recover_dtypes()[1])[0]
+    return np.frombuffer(result.cpu().numpy().tobytes(), dtype=RECOVER_RESULT)[0]
 
 
 def recover_messages_cpu(region, start: int = 0, max_messages: int = 1 << 20):
     """ambrycrc_recover_messages_cpu: the same over a region in host memory (bytes-like or numpy uint8).
     Returns (msg_off uint64[max_messages], info MESSAGE_INFO[max_messages], status uint32[max_messages],
     result: a RECOVER_RESULT record), numpy."""
-    import numpy as np
-
-    info_dt, res_dt = _recover_dtypes()
-    arr = np.frombuffer(region, dtype=np.uint8) if isinstance(region, (bytes, bytearray, memoryview)) else \
-        np.ascontiguousarray(region, dtype=np.uint8)
+    _keep, base, nbytes = host_buffer("region", region)
     n = int(max_messages) if 0 < max_messages < (1 << 31) else 0  # (the entry refuses the others)
     msg_off = np.zeros(n, dtype=np.uint64)
-    info = np.zeros(n, dtype=info_dt)
+    info = np.zeros(n, dtype=MESSAGE_INFO)
     status = np.zeros(n, dtype=np.uint32)
-    res = np.zeros(1, dtype=res_dt)
-    check(lib().ambrycrc_recover_messages_cpu(ctypes.c_void_p(arr.ctypes.data if arr.nbytes else 0), arr.nbytes,
-                                              start, max_messages, ctypes.c_void_p(msg_off.ctypes.data),
-                                              ctypes.c_void_p(info.ctypes.data), ctypes.c_void_p(status.ctypes.data),
-                                              ctypes.c_void_p(res.ctypes.data)),
+    res = np.zeros(1, dtype=RECOVER_RESULT)
+    check(lib().ambrycrc_recover_messages_cpu(base, nbytes, start, max_messages, msg_off.ctypes.data, info.ctypes.data,
+                                              status.ctypes.data, res.ctypes.data),
           "ambrycrc_recover_messages_cpu")
     return msg_off, info, status, res[0]
 
@@ -572,8 +440,6 @@ def recover_messages_cpu(region, start: int = 0, max_messages: int = 1 << 20):
 
 def shard_by_bytes(lengths, nshards: int):
     """ambrycrc_shard_by_bytes: contiguous chunk ranges [lo, hi) of about equal bytes per shard."""
-    import numpy as np
-
     lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.uint64))
     cuts = (ctypes.c_size_t * (nshards + 1))()
     check(lib().ambrycrc_shard_by_bytes(lens.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(lens), nshards,
@@ -633,12 +499,8 @@ class Comm:
 
 def _shard(base, off, length, gathered, crc_in=None, stream=None):
     torch = _torch()
-    n = off.numel()
-    _check_batch(base, off, length, n)
-    _check_u32("crc_in", crc_in, n, base.device)
-    if gathered.dtype not in (torch.int32, torch.uint32) or not gathered.is_cuda or not gathered.is_contiguous() \
-            or gathered.device != base.device:
-        raise TypeError(f"gathered must be a contiguous int32/uint32 CUDA tensor on {base.device}")
+    n = _check_batch(base, off, length, (("crc_in", crc_in),))
+    dev_tensor("gathered", gathered, (torch.int32, torch.uint32), like=base)
     s = stream if stream is not None else torch.cuda.current_stream(base.device)
     return Shard(base.device.index, base.data_ptr(), off.data_ptr(), length.data_ptr(),
                  None if crc_in is None else crc_in.data_ptr(), n, gathered.data_ptr(), s.cuda_stream)

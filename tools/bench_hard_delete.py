@@ -14,44 +14,20 @@ first full call is checked: every message deleted, every message verifies clean 
 zero. Prints one JSON line per case."""
 from __future__ import annotations
 
-import argparse
 import ctypes
-import json
-import os
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bench_common as B
 
 CASES = {"4k": (262144, 4096), "64k": (65536, 65536), "4m": (1024, 4 << 20)}
 
 
 def run(m, blob_bytes, reps):
-    import numpy as np
     import torch
 
     from ambry_amd import device as D
-    from ambry_amd.messages import PUT_DESC_DTYPE, PutMessage, layout, serialize_dev
-    from bench_put import _props_tensor
 
-    key_len, props_len, um_len = 24, 94, 1000
-    L, fo = layout(PutMessage(key=bytes(key_len), props=bytes(props_len), usermeta=bytes(um_len),
-                              blob=bytes(blob_bytes)))
-    descs = np.zeros(m, dtype=PUT_DESC_DTYPE)
-    idx = np.arange(m, dtype=np.uint64)
-    descs["out_off"] = idx * L
-    descs["blob_len"] = blob_bytes
-    descs["key_len"], descs["props_len"], descs["usermeta_len"] = key_len, props_len, um_len
-    descs["enckey_len"] = -1
-    descs["header_version"] = 3
-    region = torch.empty(m * L, dtype=torch.uint8, device="cuda")
-    D.fill_random(region[: (m * L) // 16 * 16], 3, 0)
-    p0 = fo["props"]
-    region.view(m, L)[:, p0:p0 + props_len] = _props_tensor(torch)
-    serialize_dev(torch.from_numpy(descs.view(np.uint8).copy()).cuda(), region)  # in place: random fields
-    offs = torch.from_numpy((idx * L).astype(np.int64)).cuda()
+    um_len = 1000
+    region, offs, L, fo, _ = B.stored_puts(m, blob_bytes, um_len=um_len)
     saved = region.clone()
     zeroed = m * (um_len + blob_bytes)
     flat = torch.empty(zeroed, dtype=torch.uint8, device="cuda")
@@ -83,30 +59,14 @@ def run(m, blob_bytes, reps):
         "memset": (False, lambda: hip.hipMemsetAsync(flat.data_ptr(), 0, zeroed, stream)),
     }
 
-    def once(name):
-        restore, fn = calls[name]
-        if restore:
+    def restore(name):  # before every call that reads the records, outside the timed span
+        if calls[name][0]:
             region.copy_(saved)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1)
 
-    t_pre = time.perf_counter()
-    while time.perf_counter() - t_pre < 0.5:
-        for name in calls:
-            once(name)
-    times = {name: [] for name in calls}
-    for _ in range(reps):  # interleaved: every call sees the same machine state over the run
-        for name in calls:
-            times[name].append(once(name))
-    ms = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
-    lo = {name: min(t) for name, t in times.items()}
+    ms, lo, _ = B.time_interleaved({k: v[1] for k, v in calls.items()}, reps, prepare=restore)
     return {"case": f"hard delete {m} x PUT({blob_bytes} B blob)", "messages": m, "region_bytes": m * L,
             "zeroed_bytes": zeroed, "reps": reps,
-            "ms_median": {k: round(x, 4) for k, x in ms.items()}, "ms_min": {k: round(x, 4) for k, x in lo.items()},
+            "ms_median": B.rounded(ms), "ms_min": B.rounded(lo),
             "memset_GBps": round(zeroed / (ms["memset"] / 1e3) / 1e9, 1),
             "fill_call_GBps_zeroed": round(zeroed / (ms["fill"] / 1e3) / 1e9, 1),
             "fill_call_over_memset": round(ms["fill"] / ms["memset"], 3),
@@ -116,29 +76,5 @@ def run(m, blob_bytes, reps):
                       "bytes outside the two records unchanged"}
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--cases", default="4k,64k,4m", help="comma list of %s" % ",".join(CASES))
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default=None, help="append the JSON lines to this file")
-    args = ap.parse_args()
-    import torch
-
-    from ambry_amd import device as D
-
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_hard_delete: needs a GPU (no CPU fallback for a timing)")
-    torch.cuda.set_device(0)
-    D.init(0)
-    for name in args.cases.split(","):
-        m, blob = CASES[name]
-        line = json.dumps(run(m, blob, args.reps))
-        print(line, flush=True)
-        if args.out:
-            with open(args.out, "a") as f:
-                f.write(line + "\n")
-        torch.cuda.empty_cache()
-
-
 if __name__ == "__main__":
-    main()
+    B.main("bench_hard_delete", __doc__, CASES, "4k,64k,4m", 20, run, only=False)

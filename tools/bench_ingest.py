@@ -14,17 +14,9 @@ Before anything is timed the ingest's output is asserted equal, byte for byte, t
 wire CRCs to the batch's, and every status 0. Prints one JSON line per case."""
 from __future__ import annotations
 
-import argparse
-import ctypes
-import json
-import os
 import struct
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bench_common as B
 
 CASES = {"4k": (262144, 4096), "64k": (65536, 65536), "4m": (512, 4 << 20)}
 
@@ -35,10 +27,9 @@ def run(m, blob_bytes, reps, only=None):
 
     from ambry_amd import device as D
     from ambry_amd import messages as M
-    from bench_put import props94
 
     key_len, um_len = 24, 100
-    props = props94()
+    props = B.props94()
     client = b"bench-client"
     head = struct.pack(">hhii", 0, 5, 1, len(client)) + client
     body_at = 8 + len(head)
@@ -96,9 +87,6 @@ def run(m, blob_bytes, reps, only=None):
     assert bool(torch.equal(wcrc, crc))
     assert bool(torch.equal(out[: m * L], out2))
 
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     crc_out = torch.empty(m, dtype=torch.int32, device="cuda")
 
     def two_calls():
@@ -108,32 +96,14 @@ def run(m, blob_bytes, reps, only=None):
     calls = {
         "ingest": lambda: M.ingest_put_requests_dev(wire, refs_t, out=out, workspace=ws),
         "two_calls": two_calls,
-        "memcpy": lambda: hip.hipMemcpyAsync(out.data_ptr(), wire.data_ptr(), wire.numel(), 3, stream),
+        "memcpy": B.memcpy_call(out, wire, wire.numel()),
     }
     if only:  # a profiler run of some calls alone
         calls = {k: v for k, v in calls.items() if k in only}
 
-    def once(name):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        calls[name]()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1)
-
-    t_pre = time.perf_counter()
-    while time.perf_counter() - t_pre < 0.5:
-        for name in calls:
-            once(name)
-    times = {name: [] for name in calls}
-    for _ in range(reps):  # interleaved: every call sees the same machine state over the run
-        for name in calls:
-            times[name].append(once(name))
-    ms = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
+    ms, lo, hi = B.time_interleaved(calls, reps)
     res = {"case": f"ingest {m} x PutRequest({blob_bytes} B blob)", "requests": m, "wire_bytes": m * F, "reps": reps,
-           "ms_median": {k: round(x, 4) for k, x in ms.items()},
-           "ms_min": {k: round(min(t), 4) for k, t in times.items()},
-           "ms_max": {k: round(max(t), 4) for k, t in times.items()}}
+           "ms_median": B.rounded(ms), "ms_min": B.rounded(lo), "ms_max": B.rounded(hi)}
     if not only:
         res.update({"ingest_over_two_calls": round(ms["ingest"] / ms["two_calls"], 3),
                     "ingest_over_memcpy": round(ms["ingest"] / ms["memcpy"], 3),
@@ -143,31 +113,5 @@ def run(m, blob_bytes, reps, only=None):
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--cases", default="4k,64k,4m", help="comma list of %s" % ",".join(CASES))
-    ap.add_argument("--reps", type=int, default=15)
-    ap.add_argument("--only", default=None,
-                    help="comma list of calls to time alone (ingest, two_calls, memcpy): a profiler run; no ratios")
-    ap.add_argument("--out", default=None, help="append the JSON lines to this file")
-    args = ap.parse_args()
-    import torch
-
-    from ambry_amd import device as D
-
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_ingest: needs a GPU (no CPU fallback for a timing)")
-    torch.cuda.set_device(0)
-    D.init(0)
-    for name in args.cases.split(","):
-        m, blob = CASES[name]
-        line = json.dumps(run(m, blob, args.reps, args.only.split(",") if args.only else None))
-        print(line, flush=True)
-        if args.out:
-            with open(args.out, "a") as f:
-                f.write(line + "\n")
-        torch.cuda.empty_cache()
-
-
 if __name__ == "__main__":
-    main()
+    B.main("bench_ingest", __doc__, CASES, "4k,64k,4m", 15, run)

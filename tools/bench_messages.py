@@ -25,6 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from bench_common import time_interleaved  # noqa: E402
+
 
 def load_mf():
     spec = importlib.util.spec_from_file_location("message_format", os.path.join(ROOT, "oracle", "message_format.py"))
@@ -108,20 +110,8 @@ def gpu_region(mf, m, blob_bytes, reps, variant=None, host=False, mode="region")
     assert probe or torch.equal(flagged, bad.sort().values), "corruption flags"
     assert probe or bool((status[bad] == mf.BLOB_CRC).all())
     view[bad, c0 + 7] ^= 0x20
-    t_pre = time.perf_counter()  # clock ramp (see bench.py)
-    while time.perf_counter() - t_pre < 0.3:
-        D.verify_messages(region, base, want_end=False)
-        torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        D.verify_messages(region, base, want_end=False)
-        e1.record()
-        torch.cuda.synchronize()
-        times.append(e0.elapsed_time(e1))
-    times.sort()
-    med = times[len(times) // 2]
+    med = time_interleaved({"verify": lambda: D.verify_messages(region, base, want_end=False)}, reps, warm_s=0.3)[0][
+        "verify"]  # 0.3 s of clock ramp first (see bench.py)
     res = {"config": f"verify {m} x PUT({blob_bytes} B blob)", "variant": variant,
            "mode": mode if L <= int(os.environ.get("AMBRYCRC_REGION_MAX_PER_MESSAGE", "6144")) else
                    "jobs (region > cut-off per message)", "messages": m, "region_bytes": m * L,

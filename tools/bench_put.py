@@ -10,35 +10,11 @@ ambrycrc_verify_messages_dev on all of them."""
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def props94() -> bytes:
-    """94 bytes of valid BlobPropertiesSerDe V5 (BlobPropertiesSerDe.java:83-103): ttl -1, public,
-    fixed creation time, contentType / ownerId / serviceId strings, account 101, container 5, not
-    encrypted, three null strings. The message verify parses the properties (deserializeBlobAll),
-    so the fields buffer must hold real ones, not random bytes."""
-    import struct
-
-    out = struct.pack(">hqbqq", 5, -1, 0, 1_700_000_000_000, 4096)
-    for s in (b"application/octet-stream", b"owner-01", b"svc001"):
-        out += struct.pack(">i", len(s)) + s
-    out += struct.pack(">hhb", 101, 5, 0) + struct.pack(">iii", 0, 0, 0)
-    assert len(out) == 94
-    return out
-
-
-def _props_tensor(torch):
-    import numpy as np
-
-    return torch.from_numpy(np.frombuffer(props94(), dtype=np.uint8).copy()).cuda()
+from bench_common import _props_tensor, props94, stored_puts, time_interleaved  # noqa: F401 (props94: re-export)
 
 
 def run(m, blob_bytes, reps, in_place, um_len=1000, blob_shift=0):
@@ -96,20 +72,7 @@ def run(m, blob_bytes, reps, in_place, um_len=1000, blob_shift=0):
         else:
             serialize_dev(d_desc, out, fields, blobs)
 
-    t_pre = time.perf_counter()
-    while time.perf_counter() - t_pre < 0.3:
-        step()
-        torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        step()
-        e1.record()
-        torch.cuda.synchronize()
-        times.append(e0.elapsed_time(e1))
-    times.sort()
-    ms = times[len(times) // 2]
+    ms = time_interleaved({"step": step}, reps, warm_s=0.3)[0]["step"]
     msg_bytes = m * L
     # in place: one read of each message (the CRC pass); copy mode: the fields read once and the
     # message written once (the copy-through sweep CRCs what it copies)
@@ -127,47 +90,18 @@ def run_transform(m, blob_bytes, reps, verdict="device"):
     the serializer), re-serialized at V3. A dense clean V3 region takes the one-pass fast path: the
     region kernel reads each message once, verifying it, and writes it once into the output; the
     CRCs are the verified input trailers."""
-    import numpy as np
     import torch
 
     from ambry_amd import device as D
-    from ambry_amd.messages import PUT_DESC_DTYPE, PutMessage, layout, out_bound, serialize_dev, transform_dev
+    from ambry_amd.messages import out_bound, transform_dev
 
     prev = D.set_transform_verdict(0, verdict == "host")
-    key_len, props_len, um_len = 24, 94, 1000
-    L, fo = layout(PutMessage(key=bytes(key_len), props=bytes(props_len), usermeta=bytes(um_len),
-                              blob=bytes(blob_bytes)))
-    descs = np.zeros(m, dtype=PUT_DESC_DTYPE)
-    idx = np.arange(m, dtype=np.uint64)
-    descs["out_off"] = idx * L
-    descs["blob_len"] = blob_bytes
-    descs["key_len"], descs["props_len"], descs["usermeta_len"] = key_len, props_len, um_len
-    descs["enckey_len"] = -1
-    descs["header_version"] = 3
-    region = torch.empty(m * L, dtype=torch.uint8, device="cuda")
-    D.fill_random(region[: (m * L) // 16 * 16], 3, 0)
-    p0 = fo["props"]
-    region.view(m, L)[:, p0:p0 + props_len] = _props_tensor(torch)
-    serialize_dev(torch.from_numpy(descs.view(np.uint8).copy()).cuda(), region)  # in place: random fields
-    offs = torch.from_numpy((idx * L).astype(np.int64)).cuda()
+    region, offs, L, _, _ = stored_puts(m, blob_bytes)
     out = torch.empty(out_bound(m * L, m), dtype=torch.uint8, device="cuda")
     _, oo, ol, st = transform_dev(region, offs, out=out)
     torch.cuda.synchronize()
     assert int(st.abs().sum().item()) == 0 and bool(torch.equal(out[: m * L], region))  # V3 -> V3: identical
-    t_pre = time.perf_counter()
-    while time.perf_counter() - t_pre < 0.3:
-        transform_dev(region, offs, out=out)
-        torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        transform_dev(region, offs, out=out)
-        e1.record()
-        torch.cuda.synchronize()
-        times.append(e0.elapsed_time(e1))
-    times.sort()
-    ms = times[len(times) // 2]
+    ms = time_interleaved({"transform": lambda: transform_dev(region, offs, out=out)}, reps, warm_s=0.3)[0]["transform"]
     # back to back: `reps` calls between two events, one synchronize (a replication thread's pattern;
     # the side-stream verdict's chain of call k then overlaps call k + 1)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -202,27 +136,13 @@ def run_transform_host(m, blob_bytes, reps, leg="gpu", verdict="device", op="tra
 
     from ambry_amd import device as D
     from ambry_amd._lib import check, lib
-    from ambry_amd.messages import PUT_DESC_DTYPE, PutMessage, layout, out_bound, serialize_dev
+    from ambry_amd.messages import out_bound
 
-    key_len, props_len, um_len = 24, 94, 1000
-    L, fo = layout(PutMessage(key=bytes(key_len), props=bytes(props_len), usermeta=bytes(um_len),
-                              blob=bytes(blob_bytes)))
-    descs = np.zeros(m, dtype=PUT_DESC_DTYPE)
-    idx = np.arange(m, dtype=np.uint64)
-    descs["out_off"] = idx * L
-    descs["blob_len"] = blob_bytes
-    descs["key_len"], descs["props_len"], descs["usermeta_len"] = key_len, props_len, um_len
-    descs["enckey_len"] = -1
-    descs["header_version"] = 3
-    region = torch.empty(m * L, dtype=torch.uint8, device="cuda")
-    D.fill_random(region[: (m * L) // 16 * 16], 3, 0)
-    p0 = fo["props"]
-    region.view(m, L)[:, p0:p0 + props_len] = _props_tensor(torch)
-    serialize_dev(torch.from_numpy(descs.view(np.uint8).copy()).cuda(), region)
+    region, _, L, _, _ = stored_puts(m, blob_bytes)
     torch.cuda.synchronize()
     host = region.cpu().numpy()  # pageable
     del region
-    offs = (idx * L).astype(np.uint64)
+    offs = np.arange(m, dtype=np.uint64) * np.uint64(L)
     cap = out_bound(m * L, m)
     out = np.empty(cap, dtype=np.uint8)
     oo, ol = np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=np.uint64)

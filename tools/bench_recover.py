@@ -18,19 +18,13 @@ rounds) come from a kernel trace of the call alone, a run of its own:
   rocprofv3 --kernel-trace --stats -- python tools/bench_recover.py --cases 4k --only recover"""
 from __future__ import annotations
 
-import argparse
 import ctypes
-import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bench_common as B
 
-CASES = {"4k": (262144, 4096, False), "1k": (262144, 1024, False), "100": (262144, 100, False),
-         "decoy": (4096, 65536, True)}
+CASES = {"4k": ("4k", 262144, 4096, False), "1k": ("1k", 262144, 1024, False), "100": ("100", 262144, 100, False),
+         "decoy": ("decoy", 4096, 65536, True)}
 
 
 def build_region(m, blob_bytes, decoy):
@@ -38,29 +32,14 @@ def build_region(m, blob_bytes, decoy):
     import numpy as np
     import torch
 
-    from ambry_amd import device as D
     from ambry_amd import messages as M
-    from bench_put import _props_tensor
 
-    key_len, props_len, um_len = 24, 94, 100
-    L, fo = M.layout(M.PutMessage(key=bytes(key_len), props=bytes(props_len), usermeta=bytes(um_len),
-                                  blob=bytes(blob_bytes)))
-    descs = np.zeros(m, dtype=M.PUT_DESC_DTYPE)
-    idx = np.arange(m, dtype=np.uint64)
-    descs["out_off"] = idx * L
-    descs["blob_len"] = blob_bytes
-    descs["key_len"], descs["props_len"], descs["usermeta_len"] = key_len, props_len, um_len
-    descs["enckey_len"] = -1
-    descs["header_version"] = 3
-    region = torch.empty(m * L, dtype=torch.uint8, device="cuda")
-    D.fill_random(region[: (m * L) // 16 * 16], 3, 0)
-    p0 = fo["props"]
-    region.view(m, L)[:, p0:p0 + props_len] = _props_tensor(torch)
-    if decoy:
+    region, _, L, fo, descs = B.stored_puts(m, blob_bytes, um_len=100)
+    if decoy:  # written over the sealed blobs, then sealed again: the in-place serializer reads what is there
         b0 = fo["blob"]
         region.view(m, L)[:, b0:b0 + blob_bytes] = torch.tensor([0, 1], dtype=torch.uint8, device="cuda").repeat(
             blob_bytes // 2)
-    M.serialize_dev(torch.from_numpy(descs.view(np.uint8).copy()).cuda(), region)  # in place: random fields
+        M.serialize_dev(torch.from_numpy(descs.view(np.uint8).copy()).cuda(), region)
     return region, L
 
 
@@ -111,28 +90,10 @@ def run(name, m, blob_bytes, decoy, reps, only=None):
     if only:  # a profiler run of some calls alone
         calls = {k: v for k, v in calls.items() if k in only}
 
-    def once(call):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        calls[call]()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1)
-
-    t_pre = time.perf_counter()
-    while time.perf_counter() - t_pre < 0.5:
-        for call in calls:
-            once(call)
-    times = {call: [] for call in calls}
-    for _ in range(reps):  # interleaved: every call sees the same machine state over the run
-        for call in calls:
-            times[call].append(once(call))
-    ms = {k: sorted(t)[len(t) // 2] for k, t in times.items()}
+    ms, lo, hi = B.time_interleaved(calls, reps)
     out = {"case": f"recover {name}: {m} x PUT({blob_bytes} B blob)", "messages": m, "region_bytes": n, "reps": reps,
            "launches_chain": 5 + (max(m - 1, 1).bit_length() + 1),
-           "ms_median": {k: round(x, 4) for k, x in ms.items()},
-           "ms_min": {k: round(min(t), 4) for k, t in times.items()},
-           "ms_max": {k: round(max(t), 4) for k, t in times.items()}, "chain_host_ms": round(chain_host_ms, 2)}
+           "ms_median": B.rounded(ms), "ms_min": B.rounded(lo), "ms_max": B.rounded(hi), "chain_host_ms": round(chain_host_ms, 2)}
     if not only:
         out.update({
             "chain_GBps": round(n / (ms["chain"] / 1e3) / 1e9, 1), "readbw_GBps": round(rb_bytes / (ms["readbw"] / 1e3) / 1e9, 1),
@@ -146,30 +107,5 @@ def run(name, m, blob_bytes, decoy, reps, only=None):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--cases", default="4k,1k,100,decoy", help="comma list of %s" % ",".join(CASES))
-    ap.add_argument("--reps", type=int, default=15)
-    ap.add_argument("--only", default=None, help="comma list of calls to time alone: a profiler run; no ratios")
-    ap.add_argument("--out", default=None, help="append the JSON lines to this file")
-    args = ap.parse_args()
-    import torch
-
-    from ambry_amd import device as D
-
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_recover: needs a GPU (no CPU fallback for a timing)")
-    torch.cuda.set_device(0)
-    D.init(0)
-    for name in args.cases.split(","):
-        m, blob, decoy = CASES[name]
-        line = json.dumps(run(name, m, blob, decoy, args.reps, args.only.split(",") if args.only else None))
-        print(line, flush=True)
-        if args.out:
-            with open(args.out, "a") as f:
-                f.write(line + "\n")
-        torch.cuda.empty_cache()
-
-
 if __name__ == "__main__":
-    main()
+    B.main("bench_recover", __doc__, CASES, "4k,1k,100,decoy", 15, run)

@@ -17,16 +17,7 @@ The first receive of each kind is checked: every payload clean, slices packed ba
 the stored content. Prints one JSON line per case."""
 from __future__ import annotations
 
-import argparse
-import ctypes
-import json
-import os
-import sys
-import time
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bench_common as B
 
 CASES = {"4k": (262144, 4096), "64k": (65536, 65536), "4m": (2048, 4 << 20)}
 
@@ -37,24 +28,9 @@ def run(m, blob_bytes, reps, only=None):
 
     from ambry_amd import device as D
     from ambry_amd import messages as M
-    from bench_put import _props_tensor
 
-    key_len, props_len, um_len = 24, 94, 1000
-    L, fo = M.layout(M.PutMessage(key=bytes(key_len), props=bytes(props_len), usermeta=bytes(um_len),
-                                  blob=bytes(blob_bytes)))
-    descs = np.zeros(m, dtype=M.PUT_DESC_DTYPE)
+    region, offs, L, fo, _ = B.stored_puts(m, blob_bytes)
     idx = np.arange(m, dtype=np.uint64)
-    descs["out_off"] = idx * L
-    descs["blob_len"] = blob_bytes
-    descs["key_len"], descs["props_len"], descs["usermeta_len"] = key_len, props_len, um_len
-    descs["enckey_len"] = -1
-    descs["header_version"] = 3
-    region = torch.empty(m * L, dtype=torch.uint8, device="cuda")
-    D.fill_random(region[: (m * L) // 16 * 16], 3, 0)
-    p0 = fo["props"]
-    region.view(m, L)[:, p0:p0 + props_len] = _props_tensor(torch)
-    M.serialize_dev(torch.from_numpy(descs.view(np.uint8).copy()).cuda(), region)  # in place: random fields
-    offs = torch.from_numpy((idx * L).astype(np.int64)).cuda()
     sizes_all = torch.full((m,), L, dtype=torch.int64, device="cuda")
     blob_rel, rec = fo["blob"] - 13, L - (fo["blob"] - 13)  # the blob record: 13-B head, content, 8-B CRC
     body = torch.empty(m * rec, dtype=torch.uint8, device="cuda")
@@ -90,56 +66,24 @@ def run(m, blob_bytes, reps, only=None):
         assert (f["out_off"] == idx * np.uint64(n)).all(), name
         assert bool(torch.equal(out[: m * n].view(m, n), content[:, a:z])), name
 
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    mode = D.get_region_mode(0)
-
-    def region_off(fn):
-        def call():
-            D.set_region_mode(0, 0)  # job mode
-            try:
-                fn()
-            finally:
-                D.set_region_mode(0, mode)
-        return call
-
     sent = torch.empty(m * rec, dtype=torch.uint8, device="cuda")
     calls = {name: recv(name) for name in kinds}
     calls.update({
         "send_blob": lambda: M.send_messages_dev(region, offs, M.SEND_BLOB, out=sent, workspace=send_ws),
-        "verify_jobs": region_off(lambda: D.verify_messages(region, offs, want_end=False)),
-        "memcpy": lambda: hip.hipMemcpyAsync(out.data_ptr(), body.data_ptr(), m * blob_bytes, 3, stream),
+        "verify_jobs": B.job_mode(lambda: D.verify_messages(region, offs, want_end=False)),
+        "memcpy": B.memcpy_call(out, body, m * blob_bytes),
     })
     if only:  # a profiler run of some calls alone
         calls = {k: v for k, v in calls.items() if k in only}
 
-    def once(name):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        calls[name]()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1)
-
-    t_pre = time.perf_counter()
-    while time.perf_counter() - t_pre < 0.5:
-        for name in calls:
-            once(name)
     if "verify_jobs" in calls:
-        once("verify_jobs")
+        calls["verify_jobs"]()
+        torch.cuda.synchronize()
         assert D.last_message_mode(0) == 0
-    times = {name: [] for name in calls}
-    for _ in range(reps):  # interleaved: every call sees the same machine state over the run
-        for name in calls:
-            times[name].append(once(name))
-    ms = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
-    lo_t = {name: min(t) for name, t in times.items()}
-    hi_t = {name: max(t) for name, t in times.items()}
+    ms, lo_t, hi_t = B.time_interleaved(calls, reps)
     res = {"case": f"recv {m} x blob record({blob_bytes} B)", "payloads": m, "body_bytes": m * rec,
            "delivered_bytes": m * blob_bytes, "reps": reps,
-           "ms_median": {k: round(x, 4) for k, x in ms.items()}, "ms_min": {k: round(x, 4) for k, x in lo_t.items()},
-           "ms_max": {k: round(x, 4) for k, x in hi_t.items()}}
+           "ms_median": B.rounded(ms), "ms_min": B.rounded(lo_t), "ms_max": B.rounded(hi_t)}
     if not only:
         allowance = hi_t["send_blob"] - lo_t["send_blob"]
         res.update({
@@ -155,30 +99,5 @@ def run(m, blob_bytes, reps, only=None):
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--cases", default="4k,64k,4m", help="comma list of %s" % ",".join(CASES))
-    ap.add_argument("--reps", type=int, default=21)
-    ap.add_argument("--only", default=None, help="comma list of calls to time alone: a profiler run; no ratios")
-    ap.add_argument("--out", default=None, help="append the JSON lines to this file")
-    args = ap.parse_args()
-    import torch
-
-    from ambry_amd import device as D
-
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_recv: needs a GPU (no CPU fallback for a timing)")
-    torch.cuda.set_device(0)
-    D.init(0)
-    for name in args.cases.split(","):
-        m, blob = CASES[name]
-        line = json.dumps(run(m, blob, args.reps, args.only.split(",") if args.only else None))
-        print(line, flush=True)
-        if args.out:
-            with open(args.out, "a") as f:
-                f.write(line + "\n")
-        torch.cuda.empty_cache()
-
-
 if __name__ == "__main__":
-    main()
+    B.main("bench_recv", __doc__, CASES, "4k,64k,4m", 21, run)

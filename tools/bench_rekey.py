@@ -15,16 +15,7 @@ sweep timing on (ambrycrc_timing_collect_each): its two CRC sweeps (the verify's
 empty here) against the whole call. Prints one JSON line per case."""
 from __future__ import annotations
 
-import argparse
-import ctypes
-import json
-import os
-import sys
-import time
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bench_common as B
 
 CASES = {"4k": (262144, 4096), "64k": (65536, 65536)}
 
@@ -35,24 +26,10 @@ def run(m, blob_bytes, reps, only=None):
 
     from ambry_amd import device as D
     from ambry_amd import messages as M
-    from bench_put import _props_tensor
 
-    key_len, props_len, um_len = 24, 94, 1000
-    L, fo = M.layout(M.PutMessage(key=bytes(key_len), props=bytes(props_len), usermeta=bytes(um_len),
-                                  blob=bytes(blob_bytes)))
-    descs = np.zeros(m, dtype=M.PUT_DESC_DTYPE)
+    key_len = 24
+    region, offs, L, _, _ = B.stored_puts(m, blob_bytes, key_len)
     idx = np.arange(m, dtype=np.uint64)
-    descs["out_off"] = idx * L
-    descs["blob_len"] = blob_bytes
-    descs["key_len"], descs["props_len"], descs["usermeta_len"] = key_len, props_len, um_len
-    descs["enckey_len"] = -1
-    descs["header_version"] = 3
-    region = torch.empty(m * L, dtype=torch.uint8, device="cuda")
-    D.fill_random(region[: (m * L) // 16 * 16], 3, 0)
-    p0 = fo["props"]
-    region.view(m, L)[:, p0:p0 + props_len] = _props_tensor(torch)
-    M.serialize_dev(torch.from_numpy(descs.view(np.uint8).copy()).cuda(), region)  # in place: random fields
-    offs = torch.from_numpy((idx * L).astype(np.int64)).cuda()
 
     grow = 16
     aux = torch.empty(m * (key_len + grow), dtype=torch.uint8, device="cuda")
@@ -78,23 +55,11 @@ def run(m, blob_bytes, reps, only=None):
         assert int(vst.abs().sum().item()) == 0, name
         assert bool(torch.equal(out[: m * Lo].view(m, Lo)[:, 40:40 + kl], aux[: m * kl].view(m, kl))), name
 
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    mode = D.get_region_mode(0)
-
-    def transform_general():
-        D.set_region_mode(0, 0)  # the general path: verify jobs with copy-through, layout, seal
-        try:
-            M.transform_dev(region, offs, out=out)
-        finally:
-            D.set_region_mode(0, mode)
-
     calls = {
         "rekey_same": lambda: M.rekey_dev(region, offs, rk["rekey_same"][1], aux, out=out, workspace=ws),
         "rekey_long": lambda: M.rekey_dev(region, offs, rk["rekey_long"][1], aux, out=out, workspace=ws),
-        "transform": transform_general,
-        "memcpy": lambda: hip.hipMemcpyAsync(out.data_ptr(), region.data_ptr(), region.numel(), 3, stream),
+        "transform": B.job_mode(lambda: M.transform_dev(region, offs, out=out)),  # verify jobs, layout, seal
+        "memcpy": B.memcpy_call(out, region, region.numel()),
     }
 
     if only:  # a profiler run of some calls alone
@@ -103,38 +68,22 @@ def run(m, blob_bytes, reps, only=None):
     else:
         ref = "rekey_same"
 
-    def once(name):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        calls[name]()
-        e1.record()
+    if "transform" in calls:
+        calls["transform"]()
         torch.cuda.synchronize()
-        return e0.elapsed_time(e1)
-
-    t_pre = time.perf_counter()
-    while time.perf_counter() - t_pre < 0.5:
-        for name in calls:
-            once(name)
-    assert "transform" not in calls or D.last_transform_path(0) == 0
-    times = {name: [] for name in calls}
-    for _ in range(reps):  # interleaved: every call sees the same machine state over the run
-        for name in calls:
-            times[name].append(once(name))
-    ms = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
-    lo = {name: min(t) for name, t in times.items()}
-    hi = {name: max(t) for name, t in times.items()}
+        assert D.last_transform_path(0) == 0
+    ms, lo, hi = B.time_interleaved(calls, reps)
     D.timing_enable(0, True)
     D.timing_collect_each(0)
-    whole = once(ref)
+    whole = B.time_interleaved({ref: calls[ref]}, 1, warm_s=0)[0][ref]
     sweeps = D.timing_collect_each(0)
     D.timing_enable(0, False)
     if only:
         return {"case": f"rekey {m} x PUT({blob_bytes} B blob)", "messages": m, "region_bytes": m * L, "reps": reps,
-                "ms_median": {k: round(x, 4) for k, x in ms.items()}, "timed_call": ref, "timed_call_ms": round(whole, 4),
+                "ms_median": B.rounded(ms), "timed_call": ref, "timed_call_ms": round(whole, 4),
                 "timed_call_sweeps_ms": [round(x, 4) for x in sweeps]}
     return {"case": f"rekey {m} x PUT({blob_bytes} B blob)", "messages": m, "region_bytes": m * L, "reps": reps,
-            "ms_median": {k: round(x, 4) for k, x in ms.items()}, "ms_min": {k: round(x, 4) for k, x in lo.items()},
-            "ms_max": {k: round(x, 4) for k, x in hi.items()},
+            "ms_median": B.rounded(ms), "ms_min": B.rounded(lo), "ms_max": B.rounded(hi),
             "rekey_same_over_transform": round(ms["rekey_same"] / ms["transform"], 3),
             "rekey_long_over_rekey_same": round(ms["rekey_long"] / ms["rekey_same"], 3),
             "rekey_same_over_memcpy": round(ms["rekey_same"] / ms["memcpy"], 3),
@@ -145,32 +94,5 @@ def run(m, blob_bytes, reps, only=None):
             "parity": "every message re-keyed, outputs clean under ambrycrc_verify_messages_dev, new keys in place"}
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--cases", default="4k,64k", help="comma list of %s" % ",".join(CASES))
-    ap.add_argument("--reps", type=int, default=15)
-    ap.add_argument("--only", default=None,
-                    help="comma list of calls to time alone (rekey_same, rekey_long, transform, memcpy): a "
-                         "profiler run; no ratios")
-    ap.add_argument("--out", default=None, help="append the JSON lines to this file")
-    args = ap.parse_args()
-    import torch
-
-    from ambry_amd import device as D
-
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_rekey: needs a GPU (no CPU fallback for a timing)")
-    torch.cuda.set_device(0)
-    D.init(0)
-    for name in args.cases.split(","):
-        m, blob = CASES[name]
-        line = json.dumps(run(m, blob, args.reps, args.only.split(",") if args.only else None))
-        print(line, flush=True)
-        if args.out:
-            with open(args.out, "a") as f:
-                f.write(line + "\n")
-        torch.cuda.empty_cache()
-
-
 if __name__ == "__main__":
-    main()
+    B.main("bench_rekey", __doc__, CASES, "4k,64k", 15, run)
