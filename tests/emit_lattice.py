@@ -25,7 +25,9 @@ import functools
 import struct
 import zlib
 
-from test_message_format import MF
+import ingest_oracle as IO
+import rekey_oracle as RK
+from msgfmt import MF
 
 KEYS = ("hv", "enc", "sv", "w", "priv", "encb", "bv", "comp", "n", "um", "meta", "repl", "bs", "ids")
 DEFAULTS = dict(hv=3, enc="none", sv=5, w=3, priv=0, encb=0, bv=3, comp=0, n=17, um=5, meta=0, repl="keep", bs="none",
@@ -170,8 +172,6 @@ def rekey_inputs():
     case says."""
     import numpy as np
 
-    import rekey_oracle as RK
-
     cs = cases()
     descs, aux = np.zeros(len(cs), dtype=RK.DESC), bytearray(b"#")
     for i, c in enumerate(cs):
@@ -194,8 +194,6 @@ def wire():
     the lowest that carries the case's fields: 3, 4 with an encryption key (an empty one reads as none), 5 with
     an isCompressed byte."""
     import numpy as np
-
-    import ingest_oracle as IO
 
     cs = cases()
     refs, buf = np.zeros(len(cs), dtype=IO.REF), bytearray()
@@ -230,3 +228,46 @@ def put_messages(version: int, big_tail: bool = False):
         exp.append(MF.put_message(m.key, m.props, m.usermeta, m.blob, version=version, enc_key=m.enckey,
                                   life=m.life_version, compressed=m.compressed, blob_type=m.blob_type))
     return msgs, exp
+
+
+# ---------------------------------------------------------------- what the oracles give over the lattice
+OUT_VERSIONS = (1, 2, 3)
+
+
+def life_of(i: int, version: int, use_life: bool):
+    return (i % 5 if use_life else None)
+
+
+@functools.lru_cache(maxsize=None)
+def transform_expected(version: int, use_life: bool, fast_only: bool = False):
+    """[(status, bytes)] of MF.transform_message over the lattice's region."""
+    stored, offs, _ = region(fast_only)
+    return [MF.transform_message(stored, o, life=life_of(i, version, use_life), version=version)
+            for i, o in enumerate(offs)]
+
+
+@functools.lru_cache(maxsize=None)
+def rekey_expected(version: int, use_life: bool):
+    stored, offs, _ = region()
+    descs, aux = rekey_inputs()
+    return [RK.rekey_message(stored, o, descs[i], aux, life=life_of(i, version, use_life), version=version)
+            for i, o in enumerate(offs)]
+
+
+@functools.lru_cache(maxsize=None)
+def ingest_expected(version: int):
+    frames, refs = wire()
+    return IO.expected(frames, refs, version)
+
+
+def assert_packed(out, oo, ol, st, exp, names):
+    """A batch's outputs against [(status, bytes)]: packed in message order from 0."""
+    pos = 0
+    for i, (est, b) in enumerate(exp):
+        assert int(st[i]) == est, "%s: status %#x, expected %#x" % (names[i], int(st[i]), est)
+        assert int(oo[i]) == pos and int(ol[i]) == len(b), "%s: placed at %d + %d, expected %d + %d" % (
+            names[i], int(oo[i]), int(ol[i]), pos, len(b))
+        have = bytes(out[pos:pos + len(b)])
+        assert have == b, "%s: output differs from byte %d of %d on" % (
+            names[i], next((k for k, (x, y) in enumerate(zip(have, b)) if x != y), min(len(have), len(b))), len(b))
+        pos += len(b)

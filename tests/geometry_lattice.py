@@ -20,7 +20,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from test_message_format import MF
+from msgfmt import MF
 
 RUN = 64                 # region_crc.h: the run grid
 LONG_RUNS = 512          # region_crc.h kLongRuns: more runs than this go to the whole wave / the grid

@@ -4,19 +4,18 @@ of the library's GF(2) shift. Shared by test_hard_delete_cpu.py and test_gpu_har
 both use: the CPU entry over a region, the damage a crash mid-write leaves, and recovery structs that must be
 refused."""
 import struct
-import zlib
 
 import numpy as np
 
-from test_message_format import MF
+from msgfmt import MF
+from oracle_common import BLOB_HEAD, crc_bad
 
 INFO = np.dtype([("blob_size", "<u8"), ("size", "<u8"), ("start", "<u4"), ("usermeta_size", "<u4"),
                  ("header_version", "<i2"), ("usermeta_version", "<i2"), ("blob_version", "<i2"), ("blob_type", "<i2")])
-BLOB_HEAD = {1: 10, 2: 12, 3: 13}
 
 
 def _crc_bit(rec: bytes, bit: int) -> int:
-    return 0 if zlib.crc32(rec[:-8]) == struct.unpack(">q", rec[-8:])[0] else bit
+    return bit if crc_bad(rec, 0, len(rec)) else 0
 
 
 def replacement(um_size: int, blob_version: int, blob_type: int, blob_size: int) -> bytes:

@@ -11,7 +11,11 @@ import functools
 import struct
 import zlib
 
-from test_message_format import MF
+import numpy as np
+
+import rekey_oracle as RK
+import send_oracle as SO
+from msgfmt import MF
 
 INV = MF.INVALID
 SLOT = ("enckey", "props", "update", "usermeta", "blob")
@@ -194,3 +198,17 @@ def cases():
     """[(name, region, offset)]: every case, the packed ones in the packed region."""
     names, region, offs = packed()
     return [(n, region, o) for n, o in zip(names, offs)] + truncated()
+
+
+# ---------------------------------------------------------------- inputs of the entries run over the lattice
+def sizes_of(region, offs):
+    """readSet.sizeInBytes for each message: the header's length where it parses, else up to the next offset."""
+    ends = list(offs[1:]) + [len(region)]
+    return [SO.header_length(region, o) or max(e - o, 0) for o, e in zip(offs, ends)]
+
+
+def rekey_desc():
+    d = np.zeros(1, dtype=RK.DESC)[0]
+    d["key_src"], d["key_len"], d["content_src"], d["props_blob_size"] = 1, 11, RK.KEEP, -1
+    d["account_id"], d["container_id"] = 77, -3
+    return d, b"." + b"new-key-xyz" + b"."

@@ -32,8 +32,6 @@ from __future__ import annotations
 
 import contextlib
 import functools
-import importlib.util
-import os
 import struct
 import zlib
 from typing import NamedTuple
@@ -41,11 +39,7 @@ from typing import NamedTuple
 import numpy as np
 
 from datagen import stream_bytes
-
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_spec = importlib.util.spec_from_file_location("message_format", os.path.join(_ROOT, "oracle", "message_format.py"))
-MF = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(MF)
+from msgfmt import MF
 
 GROWTH = 26  # AMBRYCRC_TRANSFORM_GROWTH_MAX
 MSG_NO_ROOM = 1 << 12

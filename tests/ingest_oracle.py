@@ -13,28 +13,21 @@ import zlib
 import numpy as np
 
 from datagen import stream_bytes
-from test_message_format import MF
+from msgfmt import MF
+from oracle_common import (BAD_DESC, BAD_INFO, INT_MAX, MESSAGE_INFO as INFO, NO_ROOM, NOWHERE, WIRE_CRC,
+                           add_seconds_to_epoch, place_packed)
 
 BAD_VERSION = MF.BAD_VERSION
 NOT_PUT = MF.NOT_PUT
 BAD_RECORD = MF.BAD_RECORD
-NO_ROOM = 1 << 12
 NOT_ENCODABLE = MF.NOT_ENCODABLE
-BAD_DESC = 1 << 15
-BAD_INFO = 1 << 16
-WIRE_CRC = 1 << 17
 # every refusal a wire buffer can hold (NO_ROOM comes from out_cap; the Java-int refusal needs a 2 GiB frame)
 WIRE_STATUSES = (BAD_DESC, NOT_PUT, BAD_VERSION, BAD_RECORD, WIRE_CRC, NOT_ENCODABLE, BAD_INFO)
-NOWHERE = 0xFFFFFFFFFFFFFFFF
-INT_MAX = 0x7FFFFFFF
 FIXED = 20      # size, type, version, correlationId, clientIdLen
 MIN_FRAME = 81  # FIXED + SerDe V1 with empty strings (39) + umSize + blobType + blobSize + CRC
 GROWTH_MAX = 72  # AMBRYCRC_INGEST_GROWTH_MAX
 
 REF = np.dtype([("off", "<u8"), ("key_len", "<u4"), ("reserved", "<u4")])
-INFO = np.dtype([("msg_off", "<u8"), ("size", "<u8"), ("expires_at_ms", "<i8"), ("operation_time_ms", "<i8"),
-                 ("key_rel", "<u4"), ("key_len", "<u4"), ("account_id", "<i2"), ("container_id", "<i2"),
-                 ("life_version", "<i2"), ("flags", "u1"), ("header_version", "u1")])
 
 
 # ---------------------------------------------------------------- frames
@@ -55,16 +48,6 @@ def frame(version, blob_id, props, um, blob, blob_type=0, enc_key=b"", compresse
                        len(client_id) if client_len is None else client_len) + client_id
     n = 8 + len(head) + len(body) + 8 + slack
     return struct.pack(">q", n if size is None else size) + head + body + tail + bytes([0x5A]) * slack
-
-
-def _add_seconds(epoch_ms, delta_s):
-    """Utils.addSecondsToEpochTime (Utils.java:1036-1041): toMillis saturates, the add wraps."""
-    if epoch_ms == -1 or delta_s == -1:
-        return -1
-    big = (1 << 63) - 1
-    ms = max(-big - 1, min(big, delta_s * 1000))
-    v = (epoch_ms + ms) & ((1 << 64) - 1)
-    return v - (1 << 64) if v >> 63 else v
 
 
 def ingest_request(wire: bytes, off: int, key_len: int, header_version: int = 3, reserved: int = 0):
@@ -127,7 +110,7 @@ def ingest_request(wire: bytes, off: int, key_len: int, header_version: int = 3,
     msg = MF.put_message(blob_id, props, um, blob, version=header_version,
                          enc_key=enc_key if len(enc_key) else None, life=0, compressed=compressed,
                          blob_type=blob_type)
-    info = (0, len(msg), _add_seconds(f["creation"], f["ttl"]), f["creation"], MF.HEADER_SIZE[header_version],
+    info = (0, len(msg), add_seconds_to_epoch(f["creation"], f["ttl"]), f["creation"], MF.HEADER_SIZE[header_version],
             len(blob_id), f["account"], f["container"], 0, 0, header_version)
     return 0, msg, computed, info
 
@@ -141,21 +124,19 @@ def expected(wire: bytes, refs, header_version: int = 3, out_cap=None):
     out_len = np.zeros(m, dtype=np.uint64)
     crc = np.zeros(m, dtype=np.uint32)
     info = np.zeros(m, dtype=INFO)
-    parts, run, total = [], 0, 0
-    for i, r in enumerate(refs):
-        st, msg, c, inf = ingest_request(wire, int(r["off"]), int(r["key_len"]), header_version, int(r["reserved"]))
+    res = [ingest_request(wire, int(r["off"]), int(r["key_len"]), header_version, int(r["reserved"])) for r in refs]
+    place = place_packed([len(msg) if st == 0 else None for st, msg, _, _ in res], out_cap)
+    packed = bytearray()
+    for i, ((st, msg, c, inf), at) in enumerate(zip(res, place)):
         crc[i] = c
-        if st == 0:
-            if out_cap is not None and run + len(msg) > out_cap:
-                st = NO_ROOM
-            else:
-                parts.append(bytes(run - total) + msg)  # (run == total until a message is refused for room)
-                out_off[i], out_len[i] = run, len(msg)
-                info[i] = (run,) + inf[1:]
-                total = run + len(msg)
-            run += len(msg)
+        if at is not None:
+            packed += bytes(at - len(packed)) + msg
+            out_off[i], out_len[i] = at, len(msg)
+            info[i] = (at,) + inf[1:]
+        elif st == 0:
+            st = NO_ROOM
         status[i] = st
-    return status, b"".join(parts), out_off, out_len, crc, info, total
+    return status, bytes(packed), out_off, out_len, crc, info, len(packed)
 
 
 # ---------------------------------------------------------------- wire buffers

@@ -9,16 +9,11 @@
 #include <vector>
 
 #include "../../include/ambrycrc.h"
+#include "harness_io.h"
 
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 2;
-  std::vector<unsigned char> all;
-  unsigned char buf[65536];
-  size_t got;
-  while ((got = fread(buf, 1, sizeof buf, f)) > 0) all.insert(all.end(), buf, buf + got);
-  fclose(f);
+  const std::vector<unsigned char> all = slurp(argv[1]);
   std::vector<uint64_t> offs(1 << 16);
   long runs = 0;
   // every start offset of the first 6000 bytes, full region

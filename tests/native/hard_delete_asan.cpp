@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/ambrycrc.h"
+#include "harness_io.h"
 
 static long runs = 0, bad = 0;
 
@@ -37,21 +38,9 @@ static void run(const unsigned char* msg, size_t n, const ambrycrc_hard_delete_i
   ++runs;
 }
 
-static uint64_t rng = 0x9E3779B97F4A7C15ull;
-static uint64_t next() {
-  rng = rng * 6364136223846793005ull + 1442695040888963407ull;
-  return rng >> 24;
-}
-
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 2;
-  std::vector<unsigned char> all;
-  unsigned char buf[65536];
-  size_t got;
-  while ((got = fread(buf, 1, sizeof buf, f)) > 0) all.insert(all.end(), buf, buf + got);
-  fclose(f);
+  const std::vector<unsigned char> all = slurp(argv[1]);
   std::vector<uint64_t> offs(4096);
   const size_t m = ambrycrc_chain_messages_host(all.data(), all.size(), 0, offs.data(), offs.size());
   for (size_t i = 0; i < m; ++i) {
@@ -74,7 +63,7 @@ int main(int argc, char** argv) {
     for (int t = 0; t < 300; ++t) {
       std::vector<unsigned char> x(msg);
       for (int k = 0; k < 3; ++k) {
-        const uint64_t v = next();
+        const uint64_t v = lcg_next();
         const size_t base = st != 0 || t < 100 ? 0 : t < 200 ? um : bl;
         const size_t span = base == 0 ? 64 : 24;
         const size_t at = base + (size_t)(v >> 8) % span;
@@ -88,16 +77,16 @@ int main(int argc, char** argv) {
       ambrycrc_hard_delete_info r = good;
       if (st != 0 || t >= 200) {
         unsigned char* p = (unsigned char*)&r;
-        for (size_t k = 0; k < sizeof r; ++k) p[k] = (unsigned char)next();
-        if (t & 1) r.header_version = 3, r.usermeta_version = 1, r.blob_version = (int16_t)(1 + next() % 3), r.blob_type = 0;
+        for (size_t k = 0; k < sizeof r; ++k) p[k] = (unsigned char)lcg_next();
+        if (t & 1) r.header_version = 3, r.usermeta_version = 1, r.blob_version = (int16_t)(1 + lcg_next() % 3), r.blob_type = 0;
       } else {
-        switch (next() % 6) {
-          case 0: r.usermeta_size += (uint32_t)(next() % 5) - 2; break;
-          case 1: r.blob_size += next() % 5 - 2; break;
-          case 2: r.blob_size = next() << (next() % 40); break;
-          case 3: r.blob_version = (int16_t)(next() % 6); break;
-          case 4: r.blob_type = (int16_t)(next() % 4 - 1); break;
-          default: r.usermeta_size = (uint32_t)next(); break;
+        switch (lcg_next() % 6) {
+          case 0: r.usermeta_size += (uint32_t)(lcg_next() % 5) - 2; break;
+          case 1: r.blob_size += lcg_next() % 5 - 2; break;
+          case 2: r.blob_size = lcg_next() << (lcg_next() % 40); break;
+          case 3: r.blob_version = (int16_t)(lcg_next() % 6); break;
+          case 4: r.blob_type = (int16_t)(lcg_next() % 4 - 1); break;
+          default: r.usermeta_size = (uint32_t)lcg_next(); break;
         }
       }
       run(msg.data(), msg.size(), &r);

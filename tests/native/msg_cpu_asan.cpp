@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/ambrycrc.h"
+#include "harness_io.h"
 
 static void run(const std::vector<unsigned char>& msg, long* runs) {
   unsigned char* r = (unsigned char*)malloc(msg.size() ? msg.size() : 1);
@@ -28,13 +29,7 @@ static void run(const std::vector<unsigned char>& msg, long* runs) {
 
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 2;
-  std::vector<unsigned char> all;
-  unsigned char buf[65536];
-  size_t got;
-  while ((got = fread(buf, 1, sizeof buf, f)) > 0) all.insert(all.end(), buf, buf + got);
-  fclose(f);
+  const std::vector<unsigned char> all = slurp(argv[1]);
   std::vector<uint64_t> offs(4096);
   const size_t m = ambrycrc_chain_messages_host(all.data(), all.size(), 0, offs.data(), offs.size());
   long runs = 0;

@@ -11,19 +11,9 @@
 #include <vector>
 
 #include "../../include/ambrycrc.h"
+#include "harness_io.h"
 
 static long runs = 0, bad = 0, recovered = 0;
-
-static std::vector<unsigned char> slurp(const char* path) {
-  std::vector<unsigned char> all;
-  FILE* f = fopen(path, "rb");
-  if (!f) return all;
-  unsigned char buf[65536];
-  size_t got;
-  while ((got = fread(buf, 1, sizeof buf, f)) > 0) all.insert(all.end(), buf, buf + got);
-  fclose(f);
-  return all;
-}
 
 // One call on an exactly-sized copy of the first n bytes; the chained starts are appended to *starts.
 static ambrycrc_recover_result run(const unsigned char* bytes, size_t n, uint64_t start, size_t max_m,

@@ -12,19 +12,9 @@
 #include <vector>
 
 #include "../../include/ambrycrc.h"
+#include "harness_io.h"
 
 static long runs = 0, bad = 0, written = 0;
-
-static std::vector<unsigned char> slurp(const char* path) {
-  std::vector<unsigned char> all;
-  FILE* f = fopen(path, "rb");
-  if (!f) return all;
-  unsigned char buf[65536];
-  size_t got;
-  while ((got = fread(buf, 1, sizeof buf, f)) > 0) all.insert(all.end(), buf, buf + got);
-  fclose(f);
-  return all;
-}
 
 static bool spans_ok(const ambrycrc_rekey_desc& d, uint64_t aux_len) {
   if (d.key_src > aux_len || d.key_len > aux_len - d.key_src) return false;
@@ -65,12 +55,6 @@ static void run(const unsigned char* msg, size_t n, const ambrycrc_rekey_desc& d
   free(a);
   free(r);
   ++runs;
-}
-
-static uint64_t rng = 0x9E3779B97F4A7C15ull;
-static uint64_t next() {
-  rng = rng * 6364136223846793005ull + 1442695040888963407ull;
-  return rng >> 24;
 }
 
 int main(int argc, char** argv) {
@@ -119,12 +103,12 @@ int main(int argc, char** argv) {
     for (int t = 0; t < 200; ++t) {  // random descriptors; every other one with small fields
       ambrycrc_rekey_desc x;
       unsigned char* p = (unsigned char*)&x;
-      for (size_t k = 0; k < sizeof x; ++k) p[k] = (unsigned char)next();
+      for (size_t k = 0; k < sizeof x; ++k) p[k] = (unsigned char)lcg_next();
       if (t & 1) {
-        x.key_len = (uint32_t)(next() % 100);
-        x.key_src = next() % (A + 2);
-        x.content_len = next() % 300;
-        x.content_src = (t & 2) ? UINT64_MAX : next() % (A + 2);
+        x.key_len = (uint32_t)(lcg_next() % 100);
+        x.key_src = lcg_next() % (A + 2);
+        x.content_len = lcg_next() % 300;
+        x.content_src = (t & 2) ? UINT64_MAX : lcg_next() % (A + 2);
       }
       run(msg.data(), msg.size(), x, aux.data(), A, 1 + t % 3);
     }

@@ -30,7 +30,7 @@ import numpy as np
 
 import geometry_lattice as G
 import rekey_oracle as RK
-from test_message_format import MF
+from msgfmt import MF
 
 STREAM_MAX = 6144            # crc32_kernels.h kStreamPutMax
 SUPER_BLOCK = 4096           # crc32_kernels.h kSuperBlock: 64 runs

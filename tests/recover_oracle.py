@@ -7,40 +7,17 @@ import zlib
 
 import numpy as np
 
-from test_message_format import MF
+from msgfmt import MF
+from oracle_common import BAD_INFO, LONG_MAX, MESSAGE_INFO as INFO, add_seconds_to_epoch, same
+from regions import join
 
-BAD_INFO = 1 << 16
 NO_MESSAGE = 0xFFFFFFFFFFFFFFFF
-LONG_MAX, LONG_MIN = (1 << 63) - 1, -(1 << 63)
-
-INFO = np.dtype([("msg_off", "<u8"), ("size", "<u8"), ("expires_at_ms", "<i8"), ("operation_time_ms", "<i8"),
-                 ("key_rel", "<u4"), ("key_len", "<u4"), ("account_id", "<i2"), ("container_id", "<i2"),
-                 ("life_version", "<i2"), ("flags", "u1"), ("header_version", "u1")])
 RESULT = np.dtype([("chained", "<u8"), ("recovered", "<u8"), ("end_off", "<u8"), ("end_status", "<u4"),
                    ("more", "<u4")])
 DELETED, TTL_UPDATED, UNDELETED = 1, 2, 4
 
 
 # ---------------------------------------------------------------- the oracle
-def _wrap64(x: int) -> int:
-    """A Java long after an add that may overflow."""
-    x &= (1 << 64) - 1
-    return x - (1 << 64) if x >> 63 else x
-
-
-def seconds_to_millis(d: int) -> int:
-    """TimeUnit.SECONDS.toMillis: saturates at Long.MAX_VALUE / Long.MIN_VALUE."""
-    over = LONG_MAX // 1000
-    return LONG_MAX if d > over else LONG_MIN if d < -over else d * 1000
-
-
-def add_seconds_to_epoch(epoch_ms: int, delta_s: int) -> int:
-    """Utils.addSecondsToEpochTime (Utils.java:1036-1041)."""
-    if epoch_ms == -1 or delta_s == -1:
-        return -1
-    return _wrap64(epoch_ms + seconds_to_millis(delta_s))
-
-
 def accept_header(region: bytes, off: int):
     """(0, next start) when the walk hops over the header at off, else (why it stops, None): the version,
     the header inside the region, verifyHeader, then the sizes (BlobStoreRecovery.java:51-71 and what
@@ -134,15 +111,11 @@ def assert_call(got, exp, max_m):
     """One recover call's outputs (numpy: msg_off, info, status, result) against recover()'s."""
     msg_off, info, status, res = got
     offs, sts, infos, eres = exp
-    n = len(offs)
-    assert {k: int(res[k]) for k in RESULT.names} == eres
-    assert [int(x) for x in msg_off[:n]] == offs
-    assert all(int(x) == NO_MESSAGE for x in msg_off[n:]) and len(msg_off) == max_m
-    assert [int(x) for x in status[:n]] == sts
-    assert all(int(x) == MF.BAD_LAYOUT for x in status[n:])
-    want = info_array(infos, max_m)
-    for name in INFO.names:
-        assert np.array_equal(info[name], want[name]), name
+    have = {k: int(res[k]) for k in RESULT.names}
+    assert have == eres, "result struct %s, expected %s" % (have, eres)
+    same(msg_off, np.array(offs + [NO_MESSAGE] * (max_m - len(offs)), dtype=np.uint64), "msg_off")
+    same(status, np.array(sts + [MF.BAD_LAYOUT] * (len(status) - len(sts)), dtype=np.uint32), "status")
+    same(info, info_array(infos, max_m), "info")
 
 
 # ---------------------------------------------------------------- stored messages
@@ -165,15 +138,6 @@ def put_message(key: bytes, content: bytes, hv=3, um=b"", enc_key=None, life=0, 
 
     return RK.stored_put(key, MF.blob_properties_bytes(len(content), **props), um, content, hv=hv, enc_key=enc_key,
                          life=life)
-
-
-def join(msgs):
-    """(region, starts) of messages laid end to end."""
-    offs, pos = [], 0
-    for m in msgs:
-        offs.append(pos)
-        pos += len(m)
-    return b"".join(msgs), offs
 
 
 def scan_geometry(names=("kScanBlock", "kScanWave")):
@@ -345,3 +309,13 @@ def recovery_test_region(hv: int, partial=False, ttl=9999, seed=3):
         msgs.append(last[:len(last) // 2])
     region, offs = join(msgs)
     return region, offs, [len(m) for m in msgs], now
+
+
+# (name, BlobProperties fields, the status recover gives): the expiry arithmetic's edges and a creation time below -1
+INFO_CASES = [
+    ("ttl-forever", dict(ttl=-1), 0), ("creation-forever", dict(creation_ms=-1, ttl=50), 0),
+    ("ttl-negative", dict(ttl=-5), 0), ("ttl-saturates", dict(ttl=1 << 62), 0),
+    ("wraps", dict(creation_ms=(1 << 62) + 1, ttl=1 << 62), 0), ("creation-bad", dict(creation_ms=-2), BAD_INFO),
+    ("ttl-min", dict(ttl=-(1 << 63)), 0), ("edge-over", dict(ttl=LONG_MAX // 1000 + 1, creation_ms=5), 0),
+    ("edge-at", dict(ttl=LONG_MAX // 1000, creation_ms=900), 0),
+]

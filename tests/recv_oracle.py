@@ -5,17 +5,14 @@ and of its copy-through pass. Bodies come from send_oracle.expected -- the oracl
 is checked against an independent producer. Shared by test_recv_cpu.py and test_gpu_recv.py."""
 import functools
 import struct
-import zlib
 
 import numpy as np
 
 import send_oracle as SO
-from test_message_format import MF
+from msgfmt import MF
+from oracle_common import BAD_RANGE, BLOB_HEAD as HEAD, INT_MAX, NO_ROOM, NOWHERE, crc_bad, flip as _flip, place_packed, same
 
 BLOB, ALL = SO.BLOB, SO.ALL
-NO_ROOM = 1 << 12
-BAD_RANGE = 1 << 18
-NOWHERE = 0xFFFFFFFFFFFFFFFF
 TO_END = 0xFFFFFFFFFFFFFFFF
 CRC_BITS = MF.ENCKEY_CRC | MF.PROPS_CRC | MF.USERMETA_CRC | MF.BLOB_CRC
 
@@ -23,7 +20,6 @@ INFO = np.dtype([("out_off", "<u8"), ("out_len", "<u8"), ("blob_size", "<u8"), (
                  ("enckey_rel", "<u4"), ("enckey_len", "<u4"), ("props_rel", "<u4"), ("props_len", "<u4"),
                  ("usermeta_rel", "<u4"), ("usermeta_len", "<u4"), ("blob_type", "u1"), ("compressed", "u1"),
                  ("blob_version", "u1"), ("header_version", "u1")])
-HEAD = {1: 10, 2: 12, 3: 13}
 
 
 def _zero_info():
@@ -34,11 +30,6 @@ def _zero_info():
 
 def _refused(status):
     return status, _zero_info(), None
-
-
-def _stored_crc_bad(b: bytes, lo: int, hi: int) -> bool:
-    """Bytes [lo, hi) against the unsigned big-endian long that follows them."""
-    return zlib.crc32(b[lo:hi]) != struct.unpack_from(">Q", b, hi)[0]
 
 
 def receive_payload(payload: bytes, flag: int, lo: int = 0, hi: int = TO_END):
@@ -79,7 +70,7 @@ def receive_payload(payload: bytes, flag: int, lo: int = 0, hi: int = TO_END):
     btype = 0 if bv == 1 else struct.unpack_from(">H", payload, rec + 2)[0]
     comp = 1 if bv == 3 and payload[rec + 4] == 1 else 0
     size = struct.unpack_from(">Q", payload, rec + head - 8)[0]
-    if btype >= 2 or size > 0x7FFFFFFF:
+    if btype >= 2 or size > INT_MAX:
         return _refused(MF.BAD_RECORD)
     if head + size + 8 > span:
         return _refused(MF.BAD_LAYOUT)  # the stream runs dry
@@ -87,7 +78,7 @@ def receive_payload(payload: bytes, flag: int, lo: int = 0, hi: int = TO_END):
     if end > size or lo > end:
         return _refused(BAD_RANGE)
     content = rec + head
-    if _stored_crc_bad(payload, rec, content + size):
+    if crc_bad(payload, rec, content + size + 8):
         crc_bits |= MF.BLOB_CRC
     f.update(out_off=0, out_len=end - lo, blob_size=size, content_rel=content, blob_type=btype, compressed=comp,
              blob_version=bv)
@@ -115,12 +106,16 @@ def expected(body: bytes, offs, sizes, flag: int, ranges=None, dst_off=None, out
         out_cap = sum(f["out_len"] for st, f, b in res if b is not None)
     out = np.full(out_cap, 0xA5, dtype=np.uint8)
     loose = np.zeros(out_cap, dtype=bool)
-    status, info, pos = [], np.zeros(m, dtype=INFO), 0
+    status, info = [], np.zeros(m, dtype=INFO)
+    lengths = [None if b is None else len(b) for _, _, b in res]
+    if dst_off is None:
+        place = place_packed(lengths, out_cap)
+    else:  # placed by the caller: each span alone against out_cap
+        place = [None if n is None or int(d) + n > out_cap else int(d) for n, d in zip(lengths, dst_off)]
     for i, (st, f, b) in enumerate(res):
         if b is not None:
-            at = pos if dst_off is None else int(dst_off[i])
-            pos += len(b)
-            if at <= out_cap and len(b) <= out_cap - at:
+            at = place[i]
+            if at is not None:
                 f = dict(f, out_off=at)
                 if st:
                     loose[at:at + len(b)] = True
@@ -138,13 +133,8 @@ def assert_outputs(got, exp):
     bytes inside a CRC-failed payload's own span are exempt."""
     st, info, out = got
     est, einfo, eout, loose = exp
-    if list(st) != list(est):
-        i = next(k for k, (a, b) in enumerate(zip(st, est)) if a != b)
-        raise AssertionError("status of payload %d: %#x, expected %#x" % (i, st[i], est[i]))
-    for name in INFO.names:
-        if not np.array_equal(info[name], einfo[name]):
-            i = int(np.nonzero(info[name] != einfo[name])[0][0])
-            raise AssertionError("%s of payload %d: %s, expected %s" % (name, i, info[name][i], einfo[name][i]))
+    same(list(st), list(est), "status")
+    same(info, einfo, "info")
     out = np.asarray(out)
     assert len(out) == len(eout)
     bad = np.nonzero((out != eout) & ~loose)[0]
@@ -170,16 +160,18 @@ def run_cpu(messages, body: bytes, offs, sizes, flag, ranges=None, out_cap=None)
         out_cap = sum(len(b) for _, _, b in res if b is not None)
     out = np.full(out_cap, 0xA5, dtype=np.uint8)
     status, info, pos = [], np.zeros(len(offs), dtype=INFO), 0
+    place = place_packed([None if b is None else len(b) for _, _, b in res], out_cap)
     for i, (st, f, b) in enumerate(res):
         f = f.copy()
         if b is not None:
-            at, pos = pos, pos + len(b)
-            if at + len(b) <= out_cap:
+            at = place[i]
+            if at is not None:
                 f["out_off"] = at
                 out[at:at + len(b)] = np.frombuffer(b, dtype=np.uint8)
             else:  # the call again with the room that is left: the entry's own NO_ROOM
-                st, f, b2 = messages.receive_blob_cpu(*calls[i], out_cap=max(out_cap - at, 0))
-                assert b2 is None
+                st, f, b2 = messages.receive_blob_cpu(*calls[i], out_cap=max(out_cap - pos, 0))
+                assert b2 is None, "payload %d: delivered into %d bytes of room" % (i, max(out_cap - pos, 0))
+            pos += len(b)
         status.append(st)
         info[i] = f
     return status, info, out
@@ -218,10 +210,6 @@ def some_ranges(body, offs, sizes, flag, seed=5):
 
 
 # ---------------------------------------------------------------- each rule once
-def _flip(b: bytes, at: int, bit=0x40) -> bytes:
-    return b[:at] + bytes([b[at] ^ bit]) + b[at + 1:]
-
-
 def _blob(content: bytes, bv=3, btype=0, comp=False) -> bytes:
     return MF.blob_record_v1(content) if bv == 1 else MF.blob_record(content, version=bv, blob_type=btype, compressed=comp)
 

@@ -11,14 +11,10 @@ import struct
 import numpy as np
 
 from datagen import stream_bytes
-from test_message_format import MF
+from msgfmt import MF
+from oracle_common import BAD_DESC, INT_MAX, NEEDS_CONTENT, NO_ROOM, NOWHERE, place_packed
 
-NO_ROOM = 1 << 12
-NEEDS_CONTENT = 1 << 14
-BAD_DESC = 1 << 15
 KEEP = 0xFFFFFFFFFFFFFFFF
-NOWHERE = 0xFFFFFFFFFFFFFFFF  # out_off of a message not written
-INT_MAX = 0x7FFFFFFF
 
 DESC = np.dtype([("key_src", "<u8"), ("content_src", "<u8"), ("content_len", "<u8"), ("props_blob_size", "<i8"),
                  ("key_len", "<u4"), ("account_id", "<i2"), ("container_id", "<i2")])
@@ -107,20 +103,18 @@ def rekey_message(region: bytes, off: int, d, aux: bytes, life=None, version: in
 def expected(region: bytes, offs, descs, aux: bytes, life=None, version: int = 3, out_cap=None):
     """(status, out_off, out_len lists, the packed output) of a batch: outputs in message order, a message
     past out_cap refused with NO_ROOM while still advancing the running offset."""
-    status, out_off, out_len, packed, pos = [], [], [], bytearray(), 0
-    for i, off in enumerate(offs):
-        st, b = rekey_message(region, off, descs[i], aux, None if life is None else int(life[i]), version)
-        at, n = NOWHERE, 0
-        if st == 0 and b:
-            if out_cap is None or pos + len(b) <= out_cap:
-                at, n = pos, len(b)
-                packed += bytes(pos - len(packed)) + b
-            else:
-                st = NO_ROOM
-            pos += len(b)
+    res = [rekey_message(region, off, descs[i], aux, None if life is None else int(life[i]), version)
+           for i, off in enumerate(offs)]
+    place = place_packed([len(b) if st == 0 and b else None for st, b in res], out_cap)
+    status, out_off, out_len, packed = [], [], [], bytearray()
+    for (st, b), at in zip(res, place):
+        if at is not None:
+            packed += bytes(at - len(packed)) + b
+        elif st == 0 and b:
+            st = NO_ROOM
         status.append(st)
-        out_off.append(at)
-        out_len.append(n)
+        out_off.append(NOWHERE if at is None else at)
+        out_len.append(0 if at is None else len(b))
     return status, out_off, out_len, bytes(packed)
 
 

@@ -14,8 +14,8 @@ import numpy as np
 
 import hard_delete_oracle as HD
 import rekey_oracle as RK
-from test_message_format import MF
-from test_put_serialize import expected as put_expected
+from msgfmt import MF
+from regions import put_expected
 
 T = 1201
 NOWHERE = -1  # out_off of a message not written, as the int64 the device returns
@@ -104,7 +104,7 @@ def serialize_oracle(msgs):
     from ambry_amd.messages import pack_batch
 
     descs, fields, blobs, offs, total = pack_batch(msgs)
-    outs = [put_expected(MF, m) for m in msgs]
+    outs = [put_expected(m) for m in msgs]
     assert offs == [int(x) for x in np.cumsum([0] + [len(b) for b in outs[:-1]])] and total == sum(map(len, outs))
     return descs, fields, blobs, total, np.array([len(b) for b in outs], dtype=np.int64), b"".join(outs)
 

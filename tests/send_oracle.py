@@ -2,16 +2,13 @@
 :112-242) as ambrycrc_send_messages_dev / ambrycrc_send_message_cpu define them, from oracle/message_format.py
 and zlib alone: independent of the library's parser and of its copy-through pass. Shared by test_send_cpu.py
 and test_gpu_send.py."""
-import zlib
-
 import numpy as np
 
-from test_message_format import MF
+from msgfmt import MF
+from oracle_common import NO_ROOM, NOWHERE, crc_bad as _crc_bad, flip as _flip, place_packed, refit as _refit
 
 BLOB_PROPERTIES, BLOB_USER_METADATA, BLOB, ALL, BLOB_INFO = 0, 1, 2, 3, 4
 FLAGS = (BLOB_PROPERTIES, BLOB_USER_METADATA, BLOB, ALL, BLOB_INFO)
-NO_ROOM = 1 << 12
-NOWHERE = 0xFFFFFFFFFFFFFFFF
 
 INFO = np.dtype([("out_off", "<u8"), ("send_len", "<u8"), ("rel_off", "<u4"), ("enckey_rel", "<u4"),
                  ("enckey_len", "<u4"), ("check", "<u4")])
@@ -20,11 +17,6 @@ RECORD_BITS = (MF.ENCKEY_CRC, MF.PROPS_CRC, MF.UPDATE_CRC, MF.USERMETA_CRC, MF.B
 
 def _refused(status):
     return status, dict(out_off=NOWHERE, send_len=0, rel_off=0, enckey_rel=0, enckey_len=0, check=0), None
-
-
-def _crc_bad(region, lo, hi):
-    """Record [lo, hi) of the region: its CRC against the big-endian long in its last 8 bytes."""
-    return zlib.crc32(region[lo:hi - 8]) != MF._be64(region, hi - 8)
 
 
 def send_message(region: bytes, off: int, size, flag: int):
@@ -81,35 +73,22 @@ def expected(region: bytes, offs, sizes, flag: int, out_cap=None):
     """(status list, INFO array, the packed output) of a batch: spans in message order over the sent messages,
     a span past out_cap refused with NO_ROOM (send_len 0, nowhere; rel_off, the key fields and check kept)
     while still advancing the running offset."""
-    status, info, packed, pos = [], np.zeros(len(offs), dtype=INFO), bytearray(), 0
-    for i, off in enumerate(offs):
-        st, f, b = send_message(region, int(off), None if sizes is None else int(sizes[i]), flag)
-        if st == 0:
-            if out_cap is None or pos + len(b) <= out_cap:
-                f["out_off"] = pos
-                packed += bytes(pos - len(packed)) + b
-            else:
-                st = NO_ROOM
-                f["out_off"], f["send_len"] = NOWHERE, 0
-            pos += len(b)
+    res = [send_message(region, int(off), None if sizes is None else int(sizes[i]), flag) for i, off in enumerate(offs)]
+    at = place_packed([len(b) if st == 0 else None for st, _, b in res], out_cap)
+    status, info, packed = [], np.zeros(len(offs), dtype=INFO), bytearray()
+    for i, (st, f, b) in enumerate(res):
+        if st == 0 and at[i] is None:
+            st = NO_ROOM
+            f["out_off"], f["send_len"] = NOWHERE, 0
+        elif st == 0:
+            f["out_off"] = at[i]
+            packed += bytes(at[i] - len(packed)) + b
         status.append(st)
         info[i] = tuple(f[n] for n in INFO.names)
     return status, info, bytes(packed)
 
 
 # ---------------------------------------------------------------- each rule once
-def _refit(msg: bytes, lo: int, hi: int, edit) -> bytes:
-    """msg with record [lo, hi) edited (edit(bytearray of the record)) and its CRC trailer recomputed."""
-    rec = bytearray(msg[lo:hi])
-    edit(rec)
-    rec[-8:] = MF._crc_long(bytes(rec[:-8]))
-    return msg[:lo] + bytes(rec) + msg[hi:]
-
-
-def _flip(msg: bytes, at: int) -> bytes:
-    return msg[:at] + bytes([msg[at] ^ 0x40]) + msg[at + 1:]
-
-
 def rule_cases():
     """(names, region, offsets, sizes): one message per rule of ambrycrc_send_messages_dev. sizes[i] is what a
     sized batch passes for message i (the header's own length where the rule is not about the size); a batch

@@ -6,7 +6,11 @@ import zlib
 
 import numpy as np
 import pytest
+
+import native_build
 from datagen import stream_bytes
+from msgfmt import MF
+from regions import record_level_cases, replica_region, verify_region
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -243,62 +247,42 @@ def test_host_crc_loops_under_asan(tmp_path):
     implementation forced in turn: no out-of-bounds read at any length or alignment, and
     bit-exact with zlib."""
     import shutil
-    import subprocess
 
     if not shutil.which("g++"):
         pytest.skip("g++ not available")
     exe = tmp_path / "host_crc_asan"
-    src = os.path.join(ROOT, "tests", "native", "host_crc_asan.cpp")
-    lib = os.path.join(ROOT, "ambry_amd", "csrc", "host_crc.cpp")
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", "-std=c++17", "-I" + os.path.join(ROOT, "ambry_amd", "csrc"),
-                    src, lib, "-lz", "-o", str(exe)], check=True, timeout=300)
+    native_build.build_host_sanitized("host_crc_asan.cpp", exe, sources=[os.path.join(native_build.CSRC, "host_crc.cpp")],
+                                      flags=["-lz"])
     for impl in ("slice8", "pclmul", "vpclmul"):
-        r = subprocess.run([str(exe)], env=dict(os.environ, AMBRYCRC_HOST_IMPL=impl), capture_output=True,
-                           text=True, timeout=300)
-        assert r.returncode == 0, r.stdout + r.stderr
-        assert "bad=0" in r.stdout
+        out = native_build.run_harness(exe, timeout=300, env=dict(os.environ, AMBRYCRC_HOST_IMPL=impl))
+        assert "bad=0" in out
 
 
 def test_chain_messages_host_under_asan(tmp_path):
     """ambrycrc_chain_messages_host parses untrusted log bytes: built with the library's host code
     under AddressSanitizer/UBSan (-Xarch_host, device code untouched) and run from every start
     offset and on every tail truncation of a region of mixed, partly corrupted messages."""
-    import subprocess
-
-    import native_build
-    from test_message_format import build_region
-
     if not native_build.have_toolchain():
         pytest.skip("hipcc/g++ not available")
-    region, _, _ = build_region(n=40, seed=5, corrupt_frac=0.2, big_every=10**9)
+    region, _, _ = verify_region(n=40, seed=5, corrupt_frac=0.2, big_every=10**9)
     rf = tmp_path / "region.bin"
     rf.write_bytes(region)
     exe = tmp_path / "chain_asan"
     native_build.build_sanitized("chain_asan.cpp", exe, tmp_path)
-    r = subprocess.run([str(exe), str(rf)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "runs=" in r.stdout
+    out = native_build.run_harness(exe, [rf])
+    assert "runs=" in out
 
 
 def test_message_cpu_under_asan(ambry, tmp_path):
     """ambrycrc_verify_message_cpu / ambrycrc_transform_message_cpu parse untrusted bytes: built with
     ASan + UBSan (host side) and run over every message of a region, its truncations and byte
     flips in its header and record heads (tests/native/msg_cpu_asan.cpp)."""
-    import subprocess
-
-    import native_build
-    from test_message_format import build_region
-
-    from test_gpu_transform import build_region as transform_region
-    from test_message_format import MF, record_level_cases
-
-    region, _, _ = build_region(n=30, seed=8, corrupt_frac=0.0, big_every=10**9)
+    region, _, _ = verify_region(n=30, seed=8, corrupt_frac=0.0, big_every=10**9)
     rf = tmp_path / "region.bin"
     rf.write_bytes(region)
     # properties at SerDe V1..V5 (non-canonical flags, non-ASCII strings) and the record-level cases:
     # the properties / update parsers walk data-dependent offsets
-    r2, offs2 = transform_region(MF, 40, seed=5, corrupt=False)
+    r2, offs2 = replica_region(40, seed=5, corrupt=False)
     rf2 = tmp_path / "region2.bin"  # the messages back to back (the harness chains them from offset 0)
     rf2.write_bytes(b"".join(r2[o:MF.verify_message(r2, o)[1]] for o in offs2))
     rf3 = tmp_path / "region3.bin"
@@ -306,9 +290,8 @@ def test_message_cpu_under_asan(ambry, tmp_path):
     exe = tmp_path / "msg_cpu_asan"
     native_build.build_sanitized("msg_cpu_asan.cpp", exe, tmp_path)
     for f in (rf, rf2, rf3):
-        r = subprocess.run([str(exe), str(f)], capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        assert "runs=" in r.stdout
+        out = native_build.run_harness(exe, [f])
+        assert "runs=" in out
 
 
 def test_update_iov_gather_list(ambry):

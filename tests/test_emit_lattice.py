@@ -1,16 +1,12 @@
 """Every CPU entry that writes a stored PUT message, over the writer lattice (tests/emit_lattice.py: each branch
 of the writer placed on purpose), against its oracle: status for status, byte for byte."""
-import functools
-
 import numpy as np
 import pytest
 
 import emit_lattice as EL
 import ingest_oracle as IO
-import rekey_oracle as RK
-from test_message_format import MF
-
-OUT_VERSIONS = (1, 2, 3)
+from emit_lattice import OUT_VERSIONS, assert_packed, ingest_expected, life_of, rekey_expected, transform_expected
+from msgfmt import MF
 
 
 @pytest.fixture(scope="module")
@@ -18,32 +14,6 @@ def messages(ambry):
     from ambry_amd import messages as M
 
     return M
-
-
-def life_of(i: int, version: int, use_life: bool):
-    return (i % 5 if use_life else None)
-
-
-@functools.lru_cache(maxsize=None)
-def transform_expected(version: int, use_life: bool, fast_only: bool = False):
-    """[(status, bytes)] of MF.transform_message over the lattice's region."""
-    region, offs, _ = EL.region(fast_only)
-    return [MF.transform_message(region, o, life=life_of(i, version, use_life), version=version)
-            for i, o in enumerate(offs)]
-
-
-@functools.lru_cache(maxsize=None)
-def rekey_expected(version: int, use_life: bool):
-    region, offs, _ = EL.region()
-    descs, aux = EL.rekey_inputs()
-    return [RK.rekey_message(region, o, descs[i], aux, life=life_of(i, version, use_life), version=version)
-            for i, o in enumerate(offs)]
-
-
-@functools.lru_cache(maxsize=None)
-def ingest_expected(version: int):
-    wire, refs = EL.wire()
-    return IO.expected(wire, refs, version)
 
 
 def test_lattice_places_every_branch():
@@ -105,16 +75,6 @@ def test_transform_message_cpu(messages, version):
         for i, o in enumerate(offs):
             got = messages.transform_message_cpu(buf, o, header_version=version, life=life_of(i, version, use_life))
             assert got == exp[i], cs[i].name
-
-
-def assert_packed(out, oo, ol, st, exp, names):
-    """A batch's outputs against [(status, bytes)]: packed in message order from 0."""
-    pos = 0
-    for i, (est, b) in enumerate(exp):
-        assert int(st[i]) == est, names[i]
-        assert int(oo[i]) == pos and int(ol[i]) == len(b), names[i]
-        assert bytes(out[pos:pos + len(b)]) == b, names[i]
-        pos += len(b)
 
 
 @pytest.mark.parametrize("version", OUT_VERSIONS)

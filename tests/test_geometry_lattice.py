@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import geometry_lattice as G
-from test_message_format import MF
+from msgfmt import MF
 
 
 @pytest.fixture(scope="module")

@@ -6,16 +6,12 @@ import pytest
 
 import emit_lattice as EL
 import rekey_oracle as RK
-from test_emit_lattice import OUT_VERSIONS, assert_packed, ingest_expected, rekey_expected, transform_expected
-from test_message_format import MF
+from emit_lattice import OUT_VERSIONS, assert_packed, ingest_expected, rekey_expected, transform_expected
+from gpu_buffers import dev
+from gpu_calls import assert_ingest_outputs, assert_rekey_outputs, run_ingest, run_rekey
+from msgfmt import MF
 
 pytestmark = pytest.mark.gpu
-
-
-def dev_bytes(b):
-    import torch
-
-    return torch.frombuffer(bytearray(b) or bytearray(1), dtype=torch.uint8).cuda()[:len(b)]
 
 
 def run_transform(gpu, region, offs, version, use_life):
@@ -24,7 +20,7 @@ def run_transform(gpu, region, offs, version, use_life):
     from ambry_amd.messages import transform_dev
 
     life = (np.arange(len(offs)) % 5).astype(np.int16)
-    out, oo, ol, st = transform_dev(dev_bytes(region), torch.tensor(np.asarray(offs, dtype=np.int64), device="cuda"),
+    out, oo, ol, st = transform_dev(dev(region), torch.tensor(np.asarray(offs, dtype=np.int64), device="cuda"),
                                     header_version=version, life_version=torch.from_numpy(life).cuda() if use_life else None)
     torch.cuda.synchronize()
     return out.cpu().numpy().tobytes(), oo.cpu().numpy(), ol.cpu().numpy(), st.cpu().numpy().view(np.uint32)
@@ -69,23 +65,23 @@ def test_transform_host_gpu_leg(gpu, version):
 @pytest.mark.parametrize("version", OUT_VERSIONS)
 def test_rekey(gpu, version):
     from ambry_amd import messages
-    from test_gpu_rekey import assert_outputs, run_gpu
 
     region, offs, cs = EL.region()
     descs, aux = EL.rekey_inputs()
     for life in (None, [i % 5 for i in range(len(offs))]):
         exp = RK.expected(region, offs, descs, aux, life=life, version=version)
         assert [(s, exp[3][o:o + n]) for s, o, n in zip(*exp[:3])] == rekey_expected(version, life is not None)
-        assert_outputs(run_gpu(messages, region, offs, descs, aux, shift=5, oshift=3, life=life, version=version), exp)
+        assert_rekey_outputs(run_rekey(messages, region, offs, descs, aux, shift=5, oshift=3, life=life,
+                                       version=version), exp)
 
 
 @pytest.mark.parametrize("version", OUT_VERSIONS)
 def test_ingest(gpu, version):
     from ambry_amd import messages
-    from test_gpu_ingest import assert_outputs, run_gpu
 
     wire, refs = EL.wire()
-    assert_outputs(run_gpu(messages, wire, refs, shift=3, oshift=1, version=version), ingest_expected(version))
+    assert_ingest_outputs(run_ingest(messages, wire, refs, shift=3, oshift=1, version=version),
+                          ingest_expected(version))
 
 
 @pytest.mark.parametrize("version", OUT_VERSIONS)
@@ -101,8 +97,8 @@ def test_serialize_copy_mode(gpu, version):
         descs, fields, blobs, offs, total = messages.pack_batch(msgs, gap=3)
         out = torch.full((total + 16,), 0xAA, dtype=torch.uint8, device="cuda")
         msg_len = torch.zeros(len(msgs), dtype=torch.int64, device="cuda")
-        messages.serialize_dev(torch.from_numpy(descs.view(np.uint8).reshape(-1).copy()).cuda(), out, dev_bytes(fields),
-                               dev_bytes(blobs), msg_len=msg_len)
+        messages.serialize_dev(torch.from_numpy(descs.view(np.uint8).reshape(-1).copy()).cuda(), out, dev(fields),
+                               dev(blobs), msg_len=msg_len)
         torch.cuda.synchronize()
         image = np.full(total + 16, 0xAA, dtype=np.uint8)
         for o, e in zip(offs, exp):

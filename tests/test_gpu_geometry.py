@@ -10,49 +10,14 @@ import numpy as np
 import pytest
 
 import geometry_lattice as G
-from test_message_format import MF
+from gpu_buffers import GUARD, assert_guards, assert_untouched, guarded, guarded_workspace
+from msgfmt import MF
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 64
 
 
 def lattice(which):
     return G.message_lattice() if which == "clean" else G.flipped()
-
-
-def guarded(data, shift: int = 0):
-    """(the whole tensor, the view of `data`'s bytes): 64 guard bytes of 0xA5, `shift` more, the bytes, 64 guard
-    bytes. A tensor's allocation is 64-aligned, so the view starts shift bytes past a run boundary."""
-    import torch
-
-    a = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data
-    whole = torch.full((GUARD + shift + len(a) + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    assert whole.data_ptr() % 64 == 0
-    view = whole[GUARD + shift:GUARD + shift + len(a)]
-    view.copy_(torch.from_numpy(np.array(a, copy=True)))
-    return whole, view
-
-
-def assert_untouched(whole, view, data, shift: int = 0):
-    import torch
-
-    n = view.numel()
-    assert bool((whole[:GUARD + shift] == 0xA5).all()) and bool((whole[GUARD + shift + n:] == 0xA5).all())
-    a = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data
-    assert torch.equal(view.cpu(), torch.from_numpy(np.array(a, copy=True))), "the call changed its input"
-
-
-def guarded_workspace(nbytes):
-    """(the whole tensor, the view) of a caller workspace of exactly nbytes between two 64-B guards, the workspace
-    itself filled with 0xA5 as the guards are: a call must neither rely on what it holds nor write past it."""
-    return guarded(np.full(nbytes, 0xA5, dtype=np.uint8))
-
-
-def assert_guards(whole, view):
-    n = view.numel()
-    assert bool((whole[:GUARD] == 0xA5).all()), "bytes written below the workspace"
-    assert bool((whole[GUARD + n:] == 0xA5).all()), "bytes written past the workspace"
 
 
 def assert_messages(lat, shift, order, status, msg_end, what):

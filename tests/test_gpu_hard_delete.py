@@ -9,52 +9,17 @@ import pytest
 
 import hard_delete_oracle as HD
 from datagen import stream_bytes
-from test_message_format import MF, build_region
+from gpu_buffers import assert_guards, guarded, guarded_workspace, guards_intact
+from gpu_calls import run_hard_delete
+from msgfmt import MF
+from regions import join, refused_messages, verify_region
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 64
-
-
-def place(region: bytes, shift: int = 0):
-    """(the whole tensor, the region's view in it): guards of 0xA5 around the region, which starts `shift`
-    bytes past a 64-B boundary of the allocation."""
-    import torch
-
-    buf = np.full(GUARD + shift + len(region) + GUARD, 0xA5, dtype=np.uint8)
-    buf[GUARD + shift:GUARD + shift + len(region)] = np.frombuffer(region, dtype=np.uint8)
-    whole = torch.from_numpy(buf).cuda()
-    return whole, whole[GUARD + shift:GUARD + shift + len(region)]
-
-
-def read_back(whole, shift: int, n: int) -> bytes:
-    """The region's bytes, after checking the guards."""
-    h = whole.cpu().numpy()
-    assert (h[:GUARD + shift] == 0xA5).all() and (h[GUARD + shift + n:] == 0xA5).all(), "guard bytes overwritten"
-    return h[GUARD + shift:GUARD + shift + n].tobytes()
-
-
-def to_dev(info):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(info).view(np.uint8).reshape(len(info), 32)).cuda()
-
-
-def run_gpu(gpu, region: bytes, offs, shift=0, recovery=None, plan_only=False, workspace=None):
-    import torch
-
-    whole, r = place(region, shift)
-    o = torch.tensor(np.asarray(offs, dtype=np.int64), device="cuda")
-    status, info = gpu.hard_delete_messages(r, o, recovery=None if recovery is None else to_dev(recovery),
-                                            plan_only=plan_only, workspace=workspace)
-    torch.cuda.synchronize()
-    return (status.cpu().numpy().view(np.uint32).tolist(), info.cpu().numpy().reshape(-1).view(HD.INFO),
-            read_back(whole, shift, len(region)))
 
 
 @functools.lru_cache(maxsize=None)
 def corrupt_region(seed):
-    region, offs, _ = build_region(n=300, seed=seed, corrupt_frac=0.1, big_every=17)
+    region, offs, _ = verify_region(n=300, seed=seed, corrupt_frac=0.1, big_every=17)
     return region, offs, HD.hard_delete(region, offs)
 
 
@@ -66,7 +31,7 @@ def test_region_matches_oracle_and_cpu(gpu, seed, shift):
     region, offs, (est, einfo, eout) = corrupt_region(seed)
     deleted, refused, not_put, other = HD.counts(region, offs, est)
     assert deleted >= 200 and refused >= 20 and not_put >= 20 and other >= 1, (deleted, refused, not_put, other)
-    st, info, out = run_gpu(gpu, region, offs, shift)
+    st, info, out = run_hard_delete(gpu, region, offs, shift)
     assert st == est
     assert np.array_equal(info, einfo)
     assert out == eout
@@ -78,7 +43,7 @@ def test_region_matches_oracle_and_cpu(gpu, seed, shift):
 def exact_case(m):
     """m small messages, 10 % corrupted (build_region's first message, the one with a blob of 60 KB and more,
     left out), and the oracle's answers."""
-    region, offs, _ = build_region(n=m + 1, seed=700 + m, corrupt_frac=0.1 if m > 1 else 0.0, big_every=10**9)
+    region, offs, _ = verify_region(n=m + 1, seed=700 + m, corrupt_frac=0.1 if m > 1 else 0.0, big_every=10**9)
     region, offs = region[offs[1]:], [o - offs[1] for o in offs[1:]]
     return region, offs, HD.hard_delete(region, offs)
 
@@ -88,13 +53,12 @@ def test_exact_workspace_between_guards(gpu, m):
     """A caller workspace of exactly ambrycrc_hard_delete_workspace_bytes(m) between two guards, 0xA5
     throughout: one message, and the counts on either side of one plan block (2 jobs a message: 2,048 / 2,050
     jobs). Status, info and every region byte as the oracle's; the workspace's guards intact."""
-    from test_gpu_geometry import assert_guards, guarded_workspace
 
     region, offs, (est, einfo, eout) = exact_case(m)
     deleted, refused, not_put, _ = HD.counts(region, offs, est)
     assert (deleted, refused, not_put) == (1, 0, 0) if m == 1 else deleted >= 700 and refused >= 50 and not_put >= 50
     whole, ws = guarded_workspace(gpu.hard_delete_workspace_bytes(m))
-    st, info, out = run_gpu(gpu, region, offs, shift=13, workspace=ws)
+    st, info, out = run_hard_delete(gpu, region, offs, shift=13, workspace=ws)
     assert_guards(whole, ws)
     assert st == est
     assert np.array_equal(info, einfo)
@@ -112,13 +76,12 @@ def test_alignment_grid(gpu):
                 msgs.append(MF.put_message(MF.store_key("k" * klen), MF.blob_properties_bytes(bn),
                                            stream_bytes(500 + i, 0, un).tobytes() if un else b"",
                                            stream_bytes(9000 + i, 0, bn).tobytes() if bn else b"", version=1 + i % 3))
-    offs = [int(x) for x in np.cumsum([0] + [len(x) for x in msgs[:-1]])]
-    region = b"".join(msgs)
+    region, offs = join(msgs)
     est, einfo, eout = HD.hard_delete(region, offs)
     assert {(o + int(r["start"]) + 6) % 16 for o, r in zip(offs, einfo)} == set(range(16))
     assert all(s == 0 for s in est)
     for shift in (0, 5):
-        st, info, out = run_gpu(gpu, region, offs, shift)
+        st, info, out = run_hard_delete(gpu, region, offs, shift)
         assert st == est and np.array_equal(info, einfo)
         assert out == eout
 
@@ -132,10 +95,9 @@ def test_share_boundaries(gpu):
         size = sizes.get(i, 50 + (i * 131) % 3000)
         msgs.append(MF.put_message(MF.store_key("S%d" % i), MF.blob_properties_bytes(size), b"u" * (i % 23),
                                    stream_bytes(7000 + i, 0, size).tobytes(), version=1 + i % 3))
-    offs = [int(x) for x in np.cumsum([0] + [len(x) for x in msgs[:-1]])]
-    region = b"".join(msgs)
+    region, offs = join(msgs)
     est, einfo, eout = HD.hard_delete(region, offs)
-    st, info, out = run_gpu(gpu, region, offs, shift=3)
+    st, info, out = run_hard_delete(gpu, region, offs, shift=3)
     assert st == est == [0] * 200 and np.array_equal(info, einfo)
     assert out == eout
 
@@ -144,15 +106,15 @@ def test_two_phases(gpu):
     """HardDeleter's two phases (HardDeleter.java:655-700): plan_only leaves the region as it is and returns
     the recovery info; the second call with that info, on a copy whose blob bodies were damaged in between,
     deletes every PUT without reading the record CRCs; bad recovery fields are refused."""
-    region, offs, _ = build_region(n=300, seed=2, corrupt_frac=0.0, big_every=17)
+    region, offs, _ = verify_region(n=300, seed=2, corrupt_frac=0.0, big_every=17)
     est, einfo, eout = HD.hard_delete(region, offs)
-    st, info, out = run_gpu(gpu, region, offs, plan_only=True)
+    st, info, out = run_hard_delete(gpu, region, offs, plan_only=True)
     assert st == est and np.array_equal(info, einfo) and out == region
     damaged, flipped = HD.flip_blob_bodies(region, offs, info)
     assert flipped >= 50
-    st, _, out = run_gpu(gpu, damaged, offs)
+    st, _, out = run_hard_delete(gpu, damaged, offs)
     assert sum(1 for s in st if s == MF.BLOB_CRC) == flipped
-    st, info2, out = run_gpu(gpu, damaged, offs, shift=7, recovery=info)
+    st, info2, out = run_hard_delete(gpu, damaged, offs, shift=7, recovery=info)
     assert st == est and np.array_equal(info2, einfo)
     assert out == eout
     # one bad field per message, by turns; messages left with good info are still deleted
@@ -163,7 +125,7 @@ def test_two_phases(gpu):
         rec[i] = HD.bad_recoveries(info[i])[n % 7]
     exp = HD.hard_delete(region, offs, rec)
     assert sum(1 for s in exp[0] if s == MF.BAD_RECORD) == len(puts[::2])
-    st, info3, out = run_gpu(gpu, region, offs, recovery=rec)
+    st, info3, out = run_hard_delete(gpu, region, offs, recovery=rec)
     assert st == exp[0] and np.array_equal(info3, exp[1])
     assert out == exp[2]
 
@@ -171,8 +133,8 @@ def test_two_phases(gpu):
 def test_deleted_messages_verify_clean(gpu):
     import torch
 
-    region, offs, _ = build_region(n=300, seed=3, corrupt_frac=0.0, big_every=17)
-    whole, r = place(region)
+    region, offs, _ = verify_region(n=300, seed=3, corrupt_frac=0.0, big_every=17)
+    whole, r = guarded(region)
     o = torch.tensor(np.asarray(offs, dtype=np.int64), device="cuda")
     st, _ = gpu.hard_delete_messages(r, o)
     vst, _ = gpu.verify_messages(r, o)
@@ -180,39 +142,22 @@ def test_deleted_messages_verify_clean(gpu):
     st = st.cpu().numpy().view(np.uint32)
     assert (st == 0).sum() >= 200 and set(st.tolist()) == {0, MF.NOT_PUT}
     assert (vst.cpu().numpy() == 0).all()
-    assert read_back(whole, 0, len(region)) == HD.hard_delete(region, offs)[2]
+    assert guards_intact(whole, 0, len(region)).tobytes() == HD.hard_delete(region, offs)[2]
 
 
 def test_duplicate_offset_empty_and_single(gpu):
     import torch
 
-    region, offs, _ = build_region(n=40, seed=6, corrupt_frac=0.1, big_every=10**9)
+    region, offs, _ = verify_region(n=40, seed=6, corrupt_frac=0.1, big_every=10**9)
     twice = offs + [offs[3], offs[3], offs[20]] + [len(region) + 5, len(region) - 1]  # and two past the region's end
     est, einfo, eout = HD.hard_delete(region, twice)
-    st, info, out = run_gpu(gpu, region, twice, shift=1)
+    st, info, out = run_hard_delete(gpu, region, twice, shift=1)
     assert st == est and np.array_equal(info, einfo) and out == eout
-    st, info, out = run_gpu(gpu, region, [])
+    st, info, out = run_hard_delete(gpu, region, [])
     assert st == [] and len(info) == 0 and out == region
     put = next(o for o, s in zip(offs, est) if s == 0)
-    st, info, out = run_gpu(gpu, region, [put])
+    st, info, out = run_hard_delete(gpu, region, [put])
     assert (st, out) == HD.hard_delete(region, [put])[::2] and st == [0]
-
-
-def refused_messages(n, tag):
-    """n messages a hard delete refuses, by turns: an update message (NOT_PUT), a PUT whose blob record CRC is
-    wrong (refused by the record check), a PUT whose header CRC is wrong (refused before any record is read)."""
-    out = []
-    for i in range(n):
-        key = MF.store_key("%s-%d" % (tag, i))
-        if i % 3 == 0:
-            out.append(MF.update_message(key, version=3, kind=["ttl", "delete", "undelete"][i // 3 % 3]))
-            continue
-        size = (i * 37) % 500
-        m = bytearray(MF.put_message(key, MF.blob_properties_bytes(size), b"u" * (i % 11),
-                                     stream_bytes(3000 + i, 0, size).tobytes(), version=1 + i % 3))
-        m[-1 if i % 3 == 1 else 9] ^= 0x04
-        out.append(bytes(m))
-    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -243,12 +188,11 @@ def test_runs_of_refused_messages(gpu, run, where):
         big = MF.put_message(MF.store_key("big"), MF.blob_properties_bytes(300_000), b"meta",
                              stream_bytes(77, 0, 300_000).tobytes(), version=3)
         msgs, first = puts[:650] + [big] + bad + puts[650:], 651
-    offs = [int(x) for x in np.cumsum([0] + [len(x) for x in msgs[:-1]])]
-    region = b"".join(msgs)
+    region, offs = join(msgs)
     est, einfo, eout = HD.hard_delete(region, offs)
     assert all(est[first:first + run]) and sum(1 for s in est if s) == run
     assert len({s for s in est[first:first + run]}) == 3
-    st, info, out = run_gpu(gpu, region, offs, shift=3)
+    st, info, out = run_hard_delete(gpu, region, offs, shift=3)
     assert st == est
     assert np.array_equal(info, einfo)
     assert out == eout
@@ -258,12 +202,11 @@ def test_every_message_refused(gpu):
     """No message is deleted: no fill job has any cost, the region comes back byte for byte and every info entry
     is zero."""
     msgs = refused_messages(300, "none")
-    offs = [int(x) for x in np.cumsum([0] + [len(x) for x in msgs[:-1]])]
-    region = b"".join(msgs)
+    region, offs = join(msgs)
     est, einfo, eout = HD.hard_delete(region, offs)
     assert all(est) and eout == region
     for plan_only in (False, True):
-        st, info, out = run_gpu(gpu, region, offs, shift=1, plan_only=plan_only)
+        st, info, out = run_hard_delete(gpu, region, offs, shift=1, plan_only=plan_only)
         assert st == est
         assert np.array_equal(info, np.zeros(len(offs), dtype=HD.INFO)) and np.array_equal(info, einfo)
         assert out == region
@@ -275,7 +218,7 @@ def test_graph_capture_and_replay(gpu):
     import torch
 
     region, offs, (est, einfo, eout) = corrupt_region(1)
-    whole, r = place(region)
+    whole, r = guarded(region)
     fresh = whole.clone()
     o = torch.tensor(np.asarray(offs, dtype=np.int64), device="cuda")
     ws = torch.empty(gpu.hard_delete_workspace_bytes(len(offs)), dtype=torch.uint8, device="cuda")
@@ -295,4 +238,4 @@ def test_graph_capture_and_replay(gpu):
         torch.cuda.synchronize()
         assert st.cpu().numpy().view(np.uint32).tolist() == est
         assert np.array_equal(info.cpu().numpy().reshape(-1).view(HD.INFO), einfo)
-        assert read_back(whole, 0, len(region)) == eout
+        assert guards_intact(whole, 0, len(region)).tobytes() == eout

@@ -8,8 +8,10 @@ import header_lattice as HL
 import recover_oracle as RO
 import rekey_oracle as RK
 import send_oracle as SO
-from test_header_lattice import rekey_desc, sizes_of
-from test_message_format import MF
+from gpu_buffers import dev
+from gpu_calls import assert_chain, assert_rekey_outputs, check_send, run_hard_delete, run_recover, run_rekey
+from header_lattice import rekey_desc, sizes_of
+from msgfmt import MF
 
 pytestmark = pytest.mark.gpu
 
@@ -17,12 +19,6 @@ pytestmark = pytest.mark.gpu
 def groups():
     """[(names, region, offsets)]: the packed region as one batch; each truncated region with its lead message."""
     return [HL.packed()] + [([n + "/lead", n], r, [0, o]) for n, r, o in HL.truncated()]
-
-
-def dev_region(region):
-    import torch
-
-    return torch.frombuffer(bytearray(region) or bytearray(1), dtype=torch.uint8).cuda()[:len(region)]
 
 
 def dev_offs(offs):
@@ -38,7 +34,7 @@ def test_verify(gpu, mode):
     gpu.set_region_mode(0, mode)
     try:
         for names, region, offs in groups():
-            status, end = gpu.verify_messages(dev_region(region), dev_offs(offs))
+            status, end = gpu.verify_messages(dev(region), dev_offs(offs))
             torch.cuda.synchronize()
             got = list(zip(status.cpu().numpy().view(np.uint32).tolist(), end.cpu().numpy().tolist()))
             assert got == [MF.verify_message(region, o) for o in offs], names[-1]
@@ -62,7 +58,7 @@ def test_transform(gpu):
         for version, use_life in ((3, True), (3, False), (1, True)):
             life = (np.arange(len(offs)) % 5).astype(np.int16)
             out, out_off, out_len, status = transform_dev(
-                dev_region(region), dev_offs(offs), header_version=version,
+                dev(region), dev_offs(offs), header_version=version,
                 life_version=torch.from_numpy(life).cuda() if use_life else None)
             torch.cuda.synchronize()
             # the lattice breaks the fast path's premise (dense clean V3 PUTs): it must have refused the batch
@@ -81,12 +77,10 @@ def test_transform(gpu):
 
 
 def test_hard_delete(gpu):
-    from test_gpu_hard_delete import run_gpu
-
     for names, region, offs in groups():
         exp = HD.hard_delete(region, offs)
         for plan_only in (True, False):
-            st, info, after = run_gpu(gpu, region, offs, shift=3, plan_only=plan_only)
+            st, info, after = run_hard_delete(gpu, region, offs, shift=3, plan_only=plan_only)
             assert st == exp[0], names[-1]
             assert np.array_equal(info, exp[1]), names[-1]
             assert after == (region if plan_only else exp[2]), names[-1]
@@ -94,32 +88,28 @@ def test_hard_delete(gpu):
 
 def test_rekey(gpu):
     from ambry_amd import messages
-    from test_gpu_rekey import assert_outputs, run_gpu
 
     d, aux = rekey_desc()
     for names, region, offs in groups():
         descs = np.repeat(np.asarray([d], dtype=RK.DESC), len(offs))
         for version, life in ((3, None), (1, [4] * len(offs))):
             exp = RK.expected(region, offs, descs, aux, life=life, version=version)
-            assert_outputs(run_gpu(messages, region, offs, descs, aux, shift=5, life=life, version=version), exp)
+            assert_rekey_outputs(run_rekey(messages, region, offs, descs, aux, shift=5, life=life, version=version), exp)
 
 
 @pytest.mark.parametrize("sized", [False, True], ids=["header-size", "given-size"])
 def test_send(gpu, sized):
     from ambry_amd import messages
-    from test_gpu_send import check
 
     for names, region, offs in groups():
         sizes = sizes_of(region, offs) if sized else None
         for flag in SO.FLAGS:
-            check(messages, region, offs, sizes, flag, shift=1, slack=3)
+            check_send(messages, region, offs, sizes, flag, shift=1, slack=3)
 
 
 def test_chain_and_recover(gpu):
-    from test_gpu_recover import assert_chain, run_gpu
-
     names, region, offs = HL.packed()
     starts = [(region, o) for o in offs] + [(r, o) for _, r, o in HL.truncated() if o <= len(r)]
     for region, start in starts:
-        RO.assert_call(run_gpu(gpu, region, start, 3), RO.recover(region, start, 3), 3)
-        assert_chain(run_gpu(gpu, region, start, 3, chain=True), *RO.chain_result(region, start, 3), 3)
+        RO.assert_call(run_recover(gpu, region, start, 3), RO.recover(region, start, 3), 3)
+        assert_chain(run_recover(gpu, region, start, 3, chain=True), *RO.chain_result(region, start, 3), 3)

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from datagen import stream_bytes
-from test_message_format import build_region
+from regions import dense_v3_region, verify_region
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +38,7 @@ def test_auto_policy_legs(gpu):
 
 @pytest.mark.parametrize("policy", ["cpu", "gpu"])
 def test_verify_messages_host_both_legs(gpu, policy):
-    region, offs, expect = build_region(n=500, seed=31, corrupt_frac=0.1)
+    region, offs, expect = verify_region(n=500, seed=31, corrupt_frac=0.1)
     prev = gpu.set_host_policy(0, gpu.HOST_CPU if policy == "cpu" else gpu.HOST_GPU)
     try:
         st, end = gpu.verify_messages_host(region, offs)
@@ -53,12 +53,10 @@ def test_auto_policy_message_legs(gpu, op):
     """The message entries under auto take the leg ambrycrc_host_msg_rates names for their own op
     (not the CRC batch's rates: a CPU leg parses, and for the transform copies, each message);
     results equal the oracle's either way."""
-    from test_gpu_transform import dense_v3_region
-    from test_message_format import MF
 
     from ambry_amd.messages import transform_host
 
-    region, offs = dense_v3_region(MF, 400, seed=71)
+    region, offs = dense_v3_region(400, seed=71)
     rates = gpu.host_msg_rates(0, op)
     assert rates["cpu_gibps"] > 0 and rates["gpu_gibps"] > 0
     prev = gpu.set_host_policy(0, gpu.HOST_AUTO)

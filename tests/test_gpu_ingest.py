@@ -8,11 +8,11 @@ import numpy as np
 import pytest
 
 import ingest_oracle as IO
-from test_message_format import MF
+from gpu_buffers import assert_guards, guarded, guarded_workspace, guards_intact
+from gpu_calls import assert_ingest_outputs, fetch_ingest, refs_tensor, run_ingest
+from msgfmt import MF
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 64
 
 
 @pytest.fixture(scope="module")
@@ -21,68 +21,6 @@ def messages(gpu):
 
     assert M.PUT_REQUEST_REF_DTYPE == IO.REF
     return M
-
-
-def place(data: bytes, shift: int, size=None):
-    """(the whole tensor, the view of `size` bytes in it holding `data`): guards of 0xA5 around the view, which
-    starts `shift` bytes past a 64-B boundary of the allocation; bytes of the view past `data` are 0xA5 too."""
-    import torch
-
-    size = len(data) if size is None else size
-    buf = np.full(GUARD + shift + size + GUARD, 0xA5, dtype=np.uint8)
-    buf[GUARD + shift:GUARD + shift + len(data)] = np.frombuffer(data, dtype=np.uint8)
-    whole = torch.from_numpy(buf).cuda()
-    return whole, whole[GUARD + shift:GUARD + shift + size]
-
-
-def guards_intact(whole, shift: int, size: int) -> np.ndarray:
-    h = whole.cpu().numpy()
-    assert (h[:GUARD + shift] == 0xA5).all() and (h[GUARD + shift + size:] == 0xA5).all(), "guard bytes overwritten"
-    return h[GUARD + shift:GUARD + shift + size]
-
-
-def refs_tensor(refs):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(refs).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def fetch(out_off, out_len, info, wire_crc, total, status):
-    return (status.cpu().numpy().view(np.uint32), out_off.cpu().numpy().view(np.uint64),
-            out_len.cpu().numpy().view(np.uint64), wire_crc.cpu().numpy().view(np.uint32),
-            np.frombuffer(info.cpu().numpy().tobytes(), dtype=IO.INFO), int(total.cpu()[0]))
-
-
-def run_gpu(messages, wire: bytes, refs, shift=0, oshift=0, version=3, out_cap=None, workspace=None):
-    """(status, out_off, out_len, wire_crc, info, total, the output view's bytes): guards checked around the wire
-    buffer (which must be unchanged) and the output."""
-    import torch
-
-    ww, w = place(wire, shift)
-    cap = messages.ingest_out_bound(len(wire), len(refs)) if out_cap is None else out_cap
-    ow, o = place(b"", oshift, cap)
-    res = messages.ingest_put_requests_dev(w, refs_tensor(refs), header_version=version, out=o, workspace=workspace)
-    torch.cuda.synchronize()
-    assert guards_intact(ww, shift, len(wire)).tobytes() == wire
-    return fetch(*res[1:]) + (guards_intact(ow, oshift, cap),)
-
-
-def assert_outputs(got, exp):
-    """Status, placement, wire CRC, MessageInfo, packed length and every byte of every written span."""
-    st, off, ln, crc, info, total, out = got
-    est, packed, eoff, eln, ecrc, einfo, etotal = exp
-    bad = np.nonzero(st != est)[0]
-    assert not len(bad), "request %d: status %#x, expected %#x" % (bad[0], st[bad[0]], est[bad[0]])
-    assert np.array_equal(off, eoff) and np.array_equal(ln, eln)
-    bad = np.nonzero(crc != ecrc)[0]
-    assert not len(bad), "request %d: wire CRC %08x, expected %08x" % (bad[0], crc[bad[0]], ecrc[bad[0]])
-    assert np.array_equal(info, einfo)
-    assert total == etotal
-    for i, (o, n) in enumerate(zip(eoff, eln)):
-        if n:
-            o, n = int(o), int(n)
-            assert out[o:o + n].tobytes() == packed[o:o + n], "message of request %d differs" % i
-    assert (out[etotal:] == 0xA5).all(), "bytes written past the last placed message"
 
 
 @functools.lru_cache(maxsize=None)
@@ -98,8 +36,8 @@ def test_wire_matches_oracle_and_cpu(messages, seed, shift, oshift):
     refused over every status; the wire buffer at four offsets from a 64-B boundary and the output at two."""
     wire, refs, exp = case(seed)
     IO.assert_mix(wire, refs, exp[0])
-    got = run_gpu(messages, wire, refs, shift, oshift)
-    assert_outputs(got, exp)
+    got = run_ingest(messages, wire, refs, shift, oshift)
+    assert_ingest_outputs(got, exp)
     if shift == 0:
         buf = np.frombuffer(wire, dtype=np.uint8)
         for i, r in enumerate(refs):
@@ -115,7 +53,7 @@ def test_wire_matches_oracle_and_cpu(messages, seed, shift, oshift):
 @pytest.mark.parametrize("version", [1, 2])
 def test_header_versions(messages, version):
     wire, refs, exp = case(2, version)
-    assert_outputs(run_gpu(messages, wire, refs, shift=3, oshift=1, version=version), exp)
+    assert_ingest_outputs(run_ingest(messages, wire, refs, shift=3, oshift=1, version=version), exp)
 
 
 # ---------------------------------------------------------------- the segment lattice
@@ -172,7 +110,7 @@ def test_segment_lattice(messages, fill):
     wire, refs, exp = lattice(fill)
     assert (5 * len(refs) >= 16384) == (fill > 0)
     assert not exp[0].any()
-    assert_outputs(run_gpu(messages, wire, refs, shift=0, oshift=5), exp)
+    assert_ingest_outputs(run_ingest(messages, wire, refs, shift=0, oshift=5), exp)
 
 
 # ---------------------------------------------------------------- workspaces, room, refused runs
@@ -186,13 +124,12 @@ def small_case(m):
 def test_exact_workspace_between_guards(messages, m):
     """A caller workspace of exactly ambrycrc_ingest_puts_workspace_size(m) between two guards, 0xA5 throughout:
     one request, and the counts on either side of one plan block (5 CRC jobs a request: 2,045 / 2,050 jobs)."""
-    from test_gpu_geometry import assert_guards, guarded_workspace
 
     wire, refs, exp = small_case(m)
     whole, ws = guarded_workspace(messages.ingest_workspace_size(m))
-    got = run_gpu(messages, wire, refs, shift=13, oshift=7, workspace=ws)
+    got = run_ingest(messages, wire, refs, shift=13, oshift=7, workspace=ws)
     assert_guards(whole, ws)
-    assert_outputs(got, exp)
+    assert_ingest_outputs(got, exp)
 
 
 def test_no_room_in_the_middle(messages):
@@ -202,7 +139,7 @@ def test_no_room_in_the_middle(messages):
     assert (exp[0] == IO.NO_ROOM).sum() >= 50 and exp[3].any() and exp[6] <= cap
     ends = full[2][full[3] > 0] + full[3][full[3] > 0]
     assert cap not in ends.tolist()  # the capacity ends inside a message
-    assert_outputs(run_gpu(messages, wire, refs, shift=1, oshift=3, out_cap=cap), exp)
+    assert_ingest_outputs(run_ingest(messages, wire, refs, shift=1, oshift=3, out_cap=cap), exp)
 
 
 @pytest.mark.parametrize("where", ["start", "middle", "end"])
@@ -222,14 +159,14 @@ def test_runs_of_refused_requests(messages, run, where):
     wire = b"".join(f[0] for f in frames)
     exp = IO.expected(wire, refs)
     assert exp[0][first:first + run].all() and (exp[0] != 0).sum() == run
-    assert_outputs(run_gpu(messages, wire, refs, shift=1, oshift=7), exp)
+    assert_ingest_outputs(run_ingest(messages, wire, refs, shift=1, oshift=7), exp)
 
 
 def test_all_refused_writes_nothing(messages):
     wire, refs, exp = case(2)
     bad = np.nonzero(exp[0])[0]
     assert len(set(exp[0][bad].tolist())) == len(IO.WIRE_STATUSES)
-    got = run_gpu(messages, wire, refs[bad], shift=1, oshift=1)
+    got = run_ingest(messages, wire, refs[bad], shift=1, oshift=1)
     assert np.array_equal(got[0], exp[0][bad]) and not got[2].any() and (got[1] == IO.NOWHERE).all()
     assert got[5] == 0 and (got[6] == 0xA5).all() and not got[4].view(np.uint8).any()
 
@@ -257,7 +194,7 @@ def test_round_trip_through_recover(messages):
     from ambry_amd import device as D
 
     wire, refs, exp = case(1)
-    ww, w = place(wire, 0)
+    ww, w = guarded(wire, 0)
     out, out_off, out_len, info, _, total, status = messages.ingest_put_requests_dev(w, refs_tensor(refs))
     torch.cuda.synchronize()
     n_total = int(total.cpu()[0])
@@ -310,9 +247,9 @@ def test_graph_capture_and_replay(messages):
     wire2, refs2, exp2 = case(2)
     n = max(len(wire), len(wire2))
     m = len(refs)
-    ww, w = place(wire, 0, n)
+    ww, w = guarded(wire, 0, n)
     cap = messages.ingest_out_bound(n, m)
-    ow, o = place(b"", 3, cap)
+    ow, o = guarded(b"", 3, cap)
     rt = refs_tensor(refs)
     ws = torch.empty(messages.ingest_workspace_size(m), dtype=torch.uint8, device="cuda")
     s = torch.cuda.Stream()
@@ -320,7 +257,7 @@ def test_graph_capture_and_replay(messages):
     with torch.cuda.stream(s):
         first = messages.ingest_put_requests_dev(w, rt, out=o, workspace=ws)  # loads the kernels outside the capture
         torch.cuda.synchronize()
-        assert_outputs(fetch(*first[1:]) + (guards_intact(ow, 3, cap),), exp)
+        assert_ingest_outputs(fetch_ingest(*first[1:]) + (guards_intact(ow, 3, cap),), exp)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=s):
             res = messages.ingest_put_requests_dev(w, rt, out=o, workspace=ws)
@@ -333,4 +270,4 @@ def test_graph_capture_and_replay(messages):
         torch.cuda.synchronize()
         g.replay()
         torch.cuda.synchronize()
-        assert_outputs(fetch(*res[1:]) + (guards_intact(ow, 3, cap),), want)
+        assert_ingest_outputs(fetch_ingest(*res[1:]) + (guards_intact(ow, 3, cap),), want)

@@ -10,7 +10,9 @@ import struct
 import numpy as np
 import pytest
 
-from test_message_format import MF, build_region
+from msgfmt import MF
+
+from regions import verify_region
 
 pytestmark = pytest.mark.gpu
 
@@ -59,7 +61,7 @@ def test_small_messages_unaligned_region(gpu, msg_mode, shift):
     """Small PUT / update messages (region mode engages: < 6 KiB per message) with 8 % corrupted,
     the region starting at every kind of offset from a 64-B boundary, so record ends fall on every
     residue of the run grid; status and ends bit-exact vs the oracle."""
-    region, offs, expect = build_region(n=700, seed=40 + shift, corrupt_frac=0.08, big_every=10**9)
+    region, offs, expect = verify_region(n=700, seed=40 + shift, corrupt_frac=0.08, big_every=10**9)
     assert len(region) <= 6144 * len(offs)
     st, end = run(gpu, region, offs, shift)
     assert st == [s for s, _ in expect]
@@ -71,7 +73,7 @@ def test_small_messages_unaligned_region(gpu, msg_mode, shift):
 def exact_case(m):
     """m small messages and the oracle's answers, shared by the three forms (build_region's first message, the
     one with a blob of 60 KB and more, left out)."""
-    region, offs, _ = build_region(n=m + 1, seed=500 + m, corrupt_frac=0.08 if m > 1 else 0.0, big_every=10**9)
+    region, offs, _ = verify_region(n=m + 1, seed=500 + m, corrupt_frac=0.08 if m > 1 else 0.0, big_every=10**9)
     region, offs = region[offs[1]:], [o - offs[1] for o in offs[1:]]
     return region, offs, [MF.verify_message(region, o) for o in offs]
 
@@ -81,7 +83,7 @@ def test_exact_workspace_between_guards(gpu, msg_mode, m):
     """A caller workspace of exactly ambrycrc_messages_workspace_bytes(m) between two guards, 0xA5 throughout, in
     every verify form (a region this small fits it in region mode too): one message, and the counts on either
     side of one plan block (5 jobs a message: 2,045 / 2,050 jobs). Status and ends as the oracle's."""
-    from test_gpu_geometry import assert_guards, guarded_workspace
+    from gpu_buffers import assert_guards, guarded_workspace
 
     region, offs, expect = exact_case(m)
     assert len(region) <= 6144 * m
@@ -97,7 +99,7 @@ def test_exact_workspace_between_guards(gpu, msg_mode, m):
 def test_region_mode_sparse_and_overlapping_offsets(gpu, msg_mode):
     """Messages listed out of order, one listed twice, gaps of junk between them, offsets past the
     region end: region mode sweeps every byte and still reads each record's own runs."""
-    region, offs, _ = build_region(n=300, seed=77, corrupt_frac=0.05, big_every=10**9)
+    region, offs, _ = verify_region(n=300, seed=77, corrupt_frac=0.05, big_every=10**9)
     junk = bytes(range(256)) * 3
     spaced, offs2 = bytearray(), []
     for i, o in enumerate(offs):
@@ -116,7 +118,7 @@ def test_region_mode_sparse_and_overlapping_offsets(gpu, msg_mode):
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_region_status_matches_oracle(gpu, seed):
-    region, offs, expect = build_region(n=600, seed=seed, corrupt_frac=0.1)
+    region, offs, expect = verify_region(n=600, seed=seed, corrupt_frac=0.1)
     st, end = run(gpu, region, offs)
     assert st == [s for s, _ in expect]
     assert end == [e for _, e in expect]
@@ -125,7 +127,7 @@ def test_region_status_matches_oracle(gpu, seed):
 
 def test_many_small_messages_group_phase(gpu):
     """4,000 messages = 20,000 record jobs (>= 16,384): the small records take the group phase."""
-    region, offs, expect = build_region(n=4000, seed=11, corrupt_frac=0.05, big_every=10**9)
+    region, offs, expect = verify_region(n=4000, seed=11, corrupt_frac=0.05, big_every=10**9)
     st, end = run(gpu, region, offs)
     assert st == [s for s, _ in expect]
     assert end == [e for _, e in expect]
@@ -133,7 +135,7 @@ def test_many_small_messages_group_phase(gpu):
 
 
 def test_bad_version_truncated_and_out_of_range(gpu):
-    region, offs, _ = build_region(n=50, seed=9, corrupt_frac=0.0)
+    region, offs, _ = verify_region(n=50, seed=9, corrupt_frac=0.0)
     junk = struct.pack(">h", 7) + bytes(60)  # unknown header version
     region2 = region + junk
     last_msg = MF.put_message(MF.store_key("tail"), MF.blob_properties_bytes(5000), b"m" * 10, bytes(5000))
@@ -175,7 +177,7 @@ def test_stored_crc_bytes_corrupted_group_phase(gpu, variant):
     mismatch) and lower word, on every record kind, in a batch large enough for the group
     phase (4,000 messages). Variant 29 reads the stored CRCs of group-phase records inside the
     sweep (SweepArgs::exp_fill); variant 0 reads all of them in the parse kernel."""
-    region, offs, expect = build_region(n=4000, seed=21, corrupt_frac=0.0, big_every=97)
+    region, offs, expect = verify_region(n=4000, seed=21, corrupt_frac=0.0, big_every=97)
     assert all(s == 0 for s, _ in expect)
     region = bytearray(region)
     rng = np.random.default_rng(5)
@@ -205,7 +207,7 @@ def _host_case(n_msgs, seed):
     """Region > one 64 MiB staging slab, messages listed out of order, with offsets at and past
     the region end, a message truncated by the region end and one whose header claims a size
     past it."""
-    region, offs, _ = build_region(n=n_msgs, seed=seed, corrupt_frac=0.05, big_every=3)
+    region, offs, _ = verify_region(n=n_msgs, seed=seed, corrupt_frac=0.05, big_every=3)
     region = bytearray(region)
     # a header whose total size runs past the region end (layout error, header-only read)
     huge = bytearray(MF.put_message(MF.store_key("huge"), MF.blob_properties_bytes(10), b"u", bytes(10)))
@@ -313,7 +315,7 @@ def test_verify_log_tool(gpu, tmp_path):
     spec = importlib.util.spec_from_file_location("verify_log", os.path.join(root, "tools", "verify_log.py"))
     vl = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(vl)
-    region, offs, expect = build_region(n=300, seed=4, corrupt_frac=0.0, big_every=50)
+    region, offs, expect = verify_region(n=300, seed=4, corrupt_frac=0.0, big_every=50)
     region = bytearray(region)
     for i in (7, 99, 200):  # record corruption: still chained, flagged
         v, total, rel = MF.parse_header(bytes(region[offs[i]:offs[i] + 64]), 0)
@@ -337,7 +339,7 @@ def test_verify_log_tool(gpu, tmp_path):
 def test_record_level_checks(gpu):
     """Messages whose CRCs are all valid but whose record versions / size fields / blob type are
     not what the reference's deserializers accept: BAD_VERSION / BAD_RECORD, as the oracle says."""
-    from test_message_format import record_level_cases
+    from regions import record_level_cases
 
     cases = record_level_cases()
     region, offs = bytearray(), []
@@ -360,7 +362,7 @@ def _expect_mode(gpu, msg_mode, region_len, m):
 def test_many_shares_boundary_messages(gpu, msg_mode):
     """30,000 small messages (~90 MB): every CU share boundary cuts a message, which the one-pass
     kernel defers to the tail kernel; status and ends bit-exact, and the call took the form asked."""
-    region, offs, expect = build_region(n=30000, seed=5, corrupt_frac=0.02, big_every=10**9)
+    region, offs, expect = verify_region(n=30000, seed=5, corrupt_frac=0.02, big_every=10**9)
     st, end = run(gpu, region, offs, shift=7)
     _expect_mode(gpu, msg_mode, len(region), len(offs))
     assert st == [s for s, _ in expect]
@@ -404,7 +406,7 @@ def test_unsorted_offsets_take_the_tail(gpu, msg_mode):
     """Offsets in random order over a region large enough for every CU: the one-pass kernel finds
     its messages by binary search of sorted offsets, sees they are not, and the tail kernel redoes
     every message; results identical to the sorted call's, reordered."""
-    region, offs, expect = build_region(n=6000, seed=12, corrupt_frac=0.05, big_every=10**9)
+    region, offs, expect = verify_region(n=6000, seed=12, corrupt_frac=0.05, big_every=10**9)
     perm = np.random.default_rng(2).permutation(len(offs))
     st, end = run(gpu, region, [offs[j] for j in perm])
     assert st == [expect[j][0] for j in perm]

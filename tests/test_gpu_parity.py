@@ -230,7 +230,7 @@ def test_batch_exact_workspace_between_guards(gpu, oracle, n):
     """A caller workspace of exactly ambrycrc_workspace_bytes(n) between two guards, 0xA5 throughout: one chunk,
     and the counts on either side of one plan block (2,048 chunks). With crc_in, so the scratch's last array
     (crc_stage) is written to its end. CRCs as the oracle's; both guards intact."""
-    from test_gpu_geometry import assert_guards, guarded_workspace
+    from gpu_buffers import assert_guards, guarded_workspace
 
     rng = np.random.default_rng(4100 + n)
     size = 1 << 20

@@ -10,21 +10,11 @@ the coverage, test_gpu_put_geometry.py runs it)."""
 import numpy as np
 import pytest
 
-from test_put_serialize import expected, random_messages
+from gpu_buffers import assert_guards, guarded_workspace
+from msgfmt import MF
+from regions import put_expected, random_messages
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def mf():
-    import importlib.util
-    import os
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("message_format", os.path.join(root, "oracle", "message_format.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 @pytest.fixture(autouse=True, params=["stream", "jobs"])
@@ -52,8 +42,8 @@ def _far(b, at):
     return big[at:]
 
 
-def _run(gpu, mf, msgs, out_align, field_align, gap, in_place=False, place=("key", "enckey", "props", "usermeta",
-                                                                           "blob"), far=0, workspace=None):
+def _run(gpu, msgs, out_align, field_align, gap, in_place=False, place=("key", "enckey", "props", "usermeta",
+                                                                        "blob"), far=0, workspace=None):
     """workspace: the caller's (serialize_dev has no such parameter: the C entry through lib())."""
     import ctypes
 
@@ -87,24 +77,24 @@ def _run(gpu, mf, msgs, out_align, field_align, gap, in_place=False, place=("key
     got = out.cpu().numpy().tobytes()
     exp = bytearray(b"\xAA" * total)
     for m, o in zip(msgs, offs):
-        e = expected(mf, m)
+        e = put_expected(m)
         exp[o:o + len(e)] = e
     assert got == bytes(exp)
-    assert mlen.cpu().numpy().tolist() == [len(expected(mf, m)) for m in msgs]
+    assert mlen.cpu().numpy().tolist() == [len(put_expected(m)) for m in msgs]
     status, end = gpu.verify_messages(out, torch.tensor(offs, dtype=torch.int64, device="cuda"))
     torch.cuda.synchronize()
     # BlobType has two values: a type-2 blob record fails the reader's check (AMBRYCRC_MSG_BAD_RECORD)
-    assert status.cpu().numpy().tolist() == [mf.BAD_RECORD if m.blob_type >= 2 else 0 for m in msgs]
-    assert end.cpu().numpy().tolist() == [o + len(expected(mf, m)) for o, m in zip(offs, msgs)]
+    assert status.cpu().numpy().tolist() == [MF.BAD_RECORD if m.blob_type >= 2 else 0 for m in msgs]
+    assert end.cpu().numpy().tolist() == [o + len(put_expected(m)) for o, m in zip(offs, msgs)]
 
 
 @pytest.mark.parametrize("out_align,field_align,gap", [(1, 1, 0), (16, 16, 0), (1, 7, 3), (4096, 1, 0)])
-def test_serialize_batch_copy_mode(gpu, mf, out_align, field_align, gap):
-    _run(gpu, mf, random_messages(mf, 400, seed=100 + out_align + field_align), out_align, field_align, gap)
+def test_serialize_batch_copy_mode(gpu, out_align, field_align, gap):
+    _run(gpu, random_messages(400, seed=100 + out_align + field_align), out_align, field_align, gap)
 
 
 @pytest.mark.parametrize("m", [1, 409, 410])
-def test_serialize_exact_workspace_between_guards(gpu, mf, put_form, m):
+def test_serialize_exact_workspace_between_guards(gpu, put_form, m):
     """A caller workspace of exactly ambrycrc_serialize_puts_workspace_bytes(m) between two guards, 0xA5
     throughout, in both copy-mode forms (the streamed form's run slots are the workspace's last bytes): one
     message, and the counts on either side of one plan block (5 jobs a message: 2,045 / 2,050 jobs). Small
@@ -112,28 +102,26 @@ def test_serialize_exact_workspace_between_guards(gpu, mf, put_form, m):
     in the same call. Output, lengths and the verify as the oracle's."""
     from ambry_amd._lib import lib
 
-    from test_gpu_geometry import assert_guards, guarded_workspace
-
-    msgs = random_messages(mf, m, seed=600 + m, max_blob=600)
-    long = sum(len(expected(mf, x)) > 6144 for x in msgs)
+    msgs = random_messages(m, seed=600 + m, max_blob=600)
+    long = sum(len(put_expected(x)) > 6144 for x in msgs)
     assert long == 0 if m == 1 else 0 < long < m // 8
     assert m == 1 or 0 < sum(x.blob_type >= 2 for x in msgs) < m  # the verify refuses some, accepts the rest
     whole, ws = guarded_workspace(lib().ambrycrc_serialize_puts_workspace_bytes(m))
-    _run(gpu, mf, msgs, 1, 3, 0, workspace=ws)
+    _run(gpu, msgs, 1, 3, 0, workspace=ws)
     assert_guards(whole, ws)
 
 
-def test_serialize_batch_in_place(gpu, mf):
-    _run(gpu, mf, random_messages(mf, 300, seed=7), 1, 1, 5, in_place=True)
+def test_serialize_batch_in_place(gpu):
+    _run(gpu, random_messages(300, seed=7), 1, 1, 5, in_place=True)
 
 
-def test_serialize_group_phase_batch(gpu, mf):
+def test_serialize_group_phase_batch(gpu):
     """4,000 messages = 20,000 CRC jobs (>= 16,384: the group phase takes the small records)."""
-    _run(gpu, mf, random_messages(mf, 4000, seed=9, max_blob=9000), 1, 3, 0)
+    _run(gpu, random_messages(4000, seed=9, max_blob=9000), 1, 3, 0)
 
 
 @pytest.mark.parametrize("far", [(64 << 20) + 3, (1 << 30) + 11])
-def test_serialize_class0_heavy_far_sources(gpu, mf, far):
+def test_serialize_class0_heavy_far_sources(gpu, far):
     """Round-2 fault regression (an experimental class-0 tail load read the sweep's base block, and the
     copy-through then passed base = null): 6,000 PUTs whose every field is <= 256 B (30,000 jobs, all
     in group class 0 of the copy-through sweep), sources placed `far` bytes into their allocations.
@@ -147,31 +135,31 @@ def test_serialize_class0_heavy_far_sources(gpu, mf, far):
     for i in range(6000):
         blen = int(rng.integers(0, 200))
         enc = stream_bytes(i, 5, int(rng.integers(0, 64))).tobytes() if i % 3 else None
-        msgs.append(PutMessage(key=mf.store_key("c0-%d" % i), props=mf.blob_properties_bytes(blen, service_id="s%d" % i),
+        msgs.append(PutMessage(key=MF.store_key("c0-%d" % i), props=MF.blob_properties_bytes(blen, service_id="s%d" % i),
                                usermeta=stream_bytes(i, 7 << 20, int(rng.integers(0, 120))).tobytes(),
                                blob=stream_bytes(i ^ 77, 0, blen).tobytes(), enckey=enc, header_version=3,
                                life_version=i % 4))
-    _run(gpu, mf, msgs, 1, 1, 0, far=far)
+    _run(gpu, msgs, 1, 1, 0, far=far)
 
 
-def test_serialize_large_blobs(gpu, mf):
+def test_serialize_large_blobs(gpu):
     from ambry_amd.messages import PutMessage
     from datagen import stream_bytes
 
-    msgs = [PutMessage(key=mf.store_key("big%d" % i), props=mf.blob_properties_bytes(4 << 20),
+    msgs = [PutMessage(key=MF.store_key("big%d" % i), props=MF.blob_properties_bytes(4 << 20),
                        usermeta=b"m" * 1000, blob=stream_bytes(50 + i, 0, (4 << 20) - (i % 3)).tobytes(),
                        header_version=3) for i in range(12)]
-    _run(gpu, mf, msgs, 1, 1, 0)
+    _run(gpu, msgs, 1, 1, 0)
 
 
 @pytest.mark.parametrize("place", [("blob",), ("key", "enckey", "props", "usermeta")])
-def test_serialize_batch_mixed(gpu, mf, place):
+def test_serialize_batch_mixed(gpu, place):
     """One source buffer given, the other slots already in place: the copy-through sweep copies
     the given fields and re-reads the in-place ones where they lie."""
-    _run(gpu, mf, random_messages(mf, 300, seed=13), 1, 5, 2, in_place=True, place=place)
+    _run(gpu, random_messages(300, seed=13), 1, 5, 2, in_place=True, place=place)
 
 
-def test_serialize_large_blobs_copy_through(gpu, mf):
+def test_serialize_large_blobs_copy_through(gpu):
     """Blobs of 4-17 MiB at ragged lengths: the copy-through sweep splits each over several waves'
     byte shares (segments that start mid-blob, nontemporal body stores, the trailing bytes), so
     every segment boundary's head piece and tail must land exactly."""
@@ -182,13 +170,13 @@ def test_serialize_large_blobs_copy_through(gpu, mf):
     sizes = [4 << 20, (4 << 20) + 13, (17 << 20) + 5, 3, (1 << 20) + 4109, 65536 + 1, 9 << 20]
     msgs = []
     for i, blen in enumerate(sizes * 2):
-        msgs.append(PutMessage(key=mf.store_key("big-%d" % i), props=mf.blob_properties_bytes(blen),
+        msgs.append(PutMessage(key=MF.store_key("big-%d" % i), props=MF.blob_properties_bytes(blen),
                                usermeta=stream_bytes(i, 3 << 20, 1000 + i).tobytes(),
                                blob=stream_bytes(i, 0, blen).tobytes(), header_version=3, life_version=i % 3))
-    _run(gpu, mf, msgs, 1, 7, 5)
+    _run(gpu, msgs, 1, 7, 5)
 
 
-def test_serialize_6k_messages(gpu, mf):
+def test_serialize_6k_messages(gpu):
     """Messages of 6,100 to 6,200 bytes, byte by byte (round 4's whole-message assembly cut-off, 6,144
     B; round 6's streamed form has the same cut-off, kStreamPutMax), under header versions 1-3,
     with and without an encryption key, at unaligned output offsets: every byte as the oracle lays
@@ -200,19 +188,19 @@ def test_serialize_6k_messages(gpu, mf):
     for i, want in enumerate(range(6100, 6201)):
         v = 1 + i % 3
         enc = b"k" * (i % 17) if v >= 2 and i % 2 else None
-        base = PutMessage(key=mf.store_key("cut-%d" % i), props=mf.blob_properties_bytes(10), usermeta=b"u" * (i % 7),
+        base = PutMessage(key=MF.store_key("cut-%d" % i), props=MF.blob_properties_bytes(10), usermeta=b"u" * (i % 7),
                           blob=b"", enckey=enc, header_version=v, life_version=i % 4 if v == 3 else 0)
         L0, _ = layout(base)
         blen = want - L0
-        props = mf.blob_properties_bytes(blen)
+        props = MF.blob_properties_bytes(blen)
         m = PutMessage(key=base.key, props=props, usermeta=base.usermeta, blob=stream_bytes(i, 3, blen).tobytes(),
                        enckey=enc, header_version=v, life_version=base.life_version)
         assert layout(m)[0] == want
         msgs.append(m)
-    _run(gpu, mf, msgs, 1, 3, 5)
+    _run(gpu, msgs, 1, 3, 5)
 
 
-def test_serialize_graph_capture_and_replay(gpu, mf):
+def test_serialize_graph_capture_and_replay(gpu):
     """ambrycrc_serialize_puts_dev only enqueues work, so it can be captured into a HIP graph:
     captured once over 300 PUTs in copy mode and replayed after every blob's bytes change (same
     sizes); each replay's output is the oracle's layout of the current bytes, every CRC trailer
@@ -224,7 +212,7 @@ def test_serialize_graph_capture_and_replay(gpu, mf):
     from ambry_amd.messages import pack_batch, serialize_dev
     from datagen import stream_bytes
 
-    msgs = random_messages(mf, 300, seed=21, max_blob=9000)
+    msgs = random_messages(300, seed=21, max_blob=9000)
     descs, fields, blobs, offs, total = pack_batch(msgs, out_align=1, field_align=3, gap=2)
     d, f, b = _dev(descs.tobytes()), _dev(fields), _dev(blobs)
     out = _dev(b"\xAA" * total)
@@ -244,10 +232,10 @@ def test_serialize_graph_capture_and_replay(gpu, mf):
         torch.cuda.synchronize()
         exp = bytearray(b"\xAA" * total)
         for m, o in zip(ms, offs):
-            e = expected(mf, m)
+            e = put_expected(m)
             exp[o:o + len(e)] = e
         assert out.cpu().numpy().tobytes() == bytes(exp)
-        assert mlen.cpu().numpy().tolist() == [len(expected(mf, m)) for m in ms]
+        assert mlen.cpu().numpy().tolist() == [len(put_expected(m)) for m in ms]
 
     check(msgs)
     msgs2 = [dataclasses.replace(m, blob=stream_bytes(500 + i, 11, len(m.blob)).tobytes()) if m.blob else m
@@ -258,7 +246,7 @@ def test_serialize_graph_capture_and_replay(gpu, mf):
     check(msgs2)
 
 
-def test_serialize_descriptors_out_of_output_order(gpu, mf):
+def test_serialize_descriptors_out_of_output_order(gpu):
     """Descriptors in an order unrelated to their output offsets (a permutation; messages back to back,
     so neighbours share 16-B pieces and 64-B runs but sit at distant indices, taken by different waves
     and workgroups): every message lands at its own offset byte-exact, gaps untouched, msg_len in
@@ -267,7 +255,7 @@ def test_serialize_descriptors_out_of_output_order(gpu, mf):
 
     from ambry_amd.messages import pack_batch, serialize_dev
 
-    msgs = random_messages(mf, 500, seed=31, max_blob=7000)
+    msgs = random_messages(500, seed=31, max_blob=7000)
     descs, fields, blobs, offs, total = pack_batch(msgs, out_align=1, field_align=1, gap=0)
     perm = np.random.default_rng(5).permutation(len(msgs))
     out = _dev(b"\xAA" * total)
@@ -276,13 +264,13 @@ def test_serialize_descriptors_out_of_output_order(gpu, mf):
     torch.cuda.synchronize()
     exp = bytearray(b"\xAA" * total)
     for m, o in zip(msgs, offs):
-        e = expected(mf, m)
+        e = put_expected(m)
         exp[o:o + len(e)] = e
     assert out.cpu().numpy().tobytes() == bytes(exp)
-    assert mlen.cpu().numpy().tolist() == [len(expected(mf, msgs[i])) for i in perm]
+    assert mlen.cpu().numpy().tolist() == [len(put_expected(msgs[i])) for i in perm]
 
 
-def test_serialize_streamed_after_job_batch(gpu, mf):
+def test_serialize_streamed_after_job_batch(gpu):
     """The streamed messages' job entries are only zeroed when the job path runs (a gated clear launch,
     put_layout_kernel with clear_short): a batch of long messages fills the stream's workspace with job
     entries, then a batch of the same size, mostly short with a few long, reuses it -- every byte as the
@@ -292,23 +280,23 @@ def test_serialize_streamed_after_job_batch(gpu, mf):
     from datagen import stream_bytes
 
     n = 200
-    longs = random_messages(mf, n, seed=41, max_blob=9000)
+    longs = random_messages(n, seed=41, max_blob=9000)
     longs = [dataclasses.replace(m, blob=stream_bytes(900 + i, 1, 7000 + i).tobytes(),
-                                 props=mf.blob_properties_bytes(7000 + i)) for i, m in enumerate(longs)]
-    _run(gpu, mf, longs, 1, 1, 0)
-    mixed = random_messages(mf, n, seed=43, max_blob=3000)
+                                 props=MF.blob_properties_bytes(7000 + i)) for i, m in enumerate(longs)]
+    _run(gpu, longs, 1, 1, 0)
+    mixed = random_messages(n, seed=43, max_blob=3000)
     mixed = [dataclasses.replace(m, blob=stream_bytes(700 + i, 2, 8000).tobytes(),
-                                 props=mf.blob_properties_bytes(8000)) if i % 37 == 5 else m
+                                 props=MF.blob_properties_bytes(8000)) if i % 37 == 5 else m
              for i, m in enumerate(mixed)]
-    _run(gpu, mf, mixed, 1, 3, 1)
+    _run(gpu, mixed, 1, 3, 1)
 
 
-def test_serialize_back_to_back_one_stream(gpu, mf):
-    """Back-to-back serialize calls on one stream share that stream's default workspace (serialize has
-    no side stream: every kernel runs on the caller's): 40 calls, every third batch with long messages
-    (the job path runs next to the streamed form), each into its own output, then one synchronize of
-    that stream only. A call must not read job entries a previous call left in the reused workspace:
-    every output is the oracle's layout."""
+def test_serialize_back_to_back_one_stream(gpu):
+    """Stale job entries and workspace reuse across back-to-back calls on one stream. Serialize has no side
+    stream (every kernel runs on the caller's), so the calls share that stream's default workspace: 40 calls,
+    every third batch with long messages (the job path runs next to the streamed form), each into its own
+    output, then one synchronize of that stream only. A call must not read job entries that an earlier call
+    left in the reused workspace: every output is the oracle's layout."""
     import dataclasses
 
     import torch
@@ -320,10 +308,10 @@ def test_serialize_back_to_back_one_stream(gpu, mf):
     cases = []
     with torch.cuda.stream(s):
         for c in range(40):
-            msgs = random_messages(mf, 60, seed=300 + c, max_blob=2000)
+            msgs = random_messages(60, seed=300 + c, max_blob=2000)
             if c % 3 == 1:
                 msgs = [dataclasses.replace(m, blob=stream_bytes(c * 97 + i, 4, 6500 + i).tobytes(),
-                                            props=mf.blob_properties_bytes(6500 + i)) if i % 7 == 2 else m
+                                            props=MF.blob_properties_bytes(6500 + i)) if i % 7 == 2 else m
                         for i, m in enumerate(msgs)]
             descs, fields, blobs, offs, total = pack_batch(msgs, out_align=1, field_align=1, gap=1)
             d = torch.frombuffer(bytearray(descs.tobytes()), dtype=torch.uint8).to("cuda", non_blocking=False)
@@ -336,6 +324,6 @@ def test_serialize_back_to_back_one_stream(gpu, mf):
     for msgs, offs, total, out, _ in cases:
         exp = bytearray(b"\xAA" * total)
         for m, o in zip(msgs, offs):
-            e = expected(mf, m)
+            e = put_expected(m)
             exp[o:o + len(e)] = e
         assert out.cpu().numpy().tobytes() == bytes(exp)

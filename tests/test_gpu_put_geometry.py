@@ -14,7 +14,7 @@ import pytest
 import geometry_lattice as G
 import put_lattice as P
 import send_oracle as SO
-from test_gpu_geometry import GUARD, assert_untouched, guarded
+from gpu_buffers import assert_guards, assert_untouched, guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -23,11 +23,6 @@ def _dev(a):
     import torch
 
     return torch.from_numpy(np.array(a, copy=True)).cuda()
-
-
-def assert_guards(whole, shift, n):
-    assert bool((whole[:GUARD + shift] == 0xA5).all()), "bytes written below the output"
-    assert bool((whole[GUARD + shift + n:] == 0xA5).all()), "bytes written past the output"
 
 
 def run_serialize(gpu, lat, form, shift=0, order=None, stream_max=P.STREAM_MAX, in_place=(), grid=None):
@@ -62,7 +57,7 @@ def run_serialize(gpu, lat, form, shift=0, order=None, stream_max=P.STREAM_MAX, 
         gpu.set_grid(0, prev_grid)
     msg = P.compare_image(lat, out.cpu().numpy(), shift, form, in_place)
     assert msg is None, msg
-    assert_guards(owhole, shift, lat.total)
+    assert_guards(owhole, lat.total, shift)
     assert_untouched(fwhole, fields, lat.fields)
     assert_untouched(bwhole, blobs, lat.blobs)
     assert np.array_equal(mlen.cpu().numpy(), lat.length[order])
@@ -118,7 +113,7 @@ def test_stream_lattice_graph_replay(gpu):
         torch.cuda.synchronize()
         msg = P.compare_image(lat, out.cpu().numpy(), 37, "stream", exp=image)
         assert msg is None, msg
-        assert_guards(owhole, 37, lat.total)
+        assert_guards(owhole, lat.total, 37)
         assert np.array_equal(mlen.cpu().numpy(), lat.length)
 
     check(lat.image)
@@ -195,7 +190,7 @@ def test_rekey_over_the_stored_lattice(gpu):
     assert status.cpu().numpy().view(np.uint32).tolist() == est
     assert out_off.cpu().numpy().tolist() == eoff and out_len.cpu().numpy().tolist() == eln
     assert_packed(out.cpu().numpy(), packed, eoff, "rekey", P.gather_ranges(P.rekey_jobs()))
-    assert_guards(owhole, 0, out.numel())
+    assert_guards(owhole, out.numel(), 0)
     assert_untouched(whole, region, lat.region)
     assert_untouched(awhole, auxd, aux)
     st, end = gpu.verify_messages(out, out_off)
@@ -229,7 +224,7 @@ def test_transform_general_path_over_the_stored_lattice(gpu, corrupt):
     assert np.array_equal(out_off.cpu().numpy(), eoff) and np.array_equal(out_len.cpu().numpy(), eln)
     assert_packed(out.cpu().numpy(), packed, eoff.tolist(), "transform-corrupt" if corrupt else "transform",
                   scratch_to=len(P.transform_expected(False)[3]))
-    assert_guards(owhole, 0, out.numel())
+    assert_guards(owhole, out.numel(), 0)
     assert_untouched(whole, region, src)
     placed = _dev(eoff[eoff >= 0])
     st, end = gpu.verify_messages(out, placed)
@@ -257,5 +252,5 @@ def test_send_over_the_stored_lattice(gpu, flag):
     for name in SO.INFO.names:
         assert np.array_equal(got[name], einfo[name]), name
     assert_packed(out.cpu().numpy(), packed, einfo["out_off"].astype(np.int64).tolist(), "send", flag=flag)
-    assert_guards(owhole, 3, out.numel())
+    assert_guards(owhole, out.numel(), 3)
     assert_untouched(whole, region, lat.region)

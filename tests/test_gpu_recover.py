@@ -8,8 +8,10 @@ import numpy as np
 import pytest
 
 import recover_oracle as RO
-from test_gpu_rekey import guards_intact, place
-from test_message_format import MF
+import rekey_oracle as RK
+from gpu_buffers import assert_guards, dev as to_dev, guarded, guarded_workspace, guards_intact
+from gpu_calls import assert_chain, copies, recover_to_numpy, run_recover
+from msgfmt import MF
 
 pytestmark = pytest.mark.gpu
 
@@ -22,32 +24,6 @@ def dev(gpu):
     return D
 
 
-def to_numpy(out):
-    """A device call's tensors as the CPU entry's numpy arrays."""
-    if len(out) == 2:
-        return out[0].cpu().numpy().view(np.uint64), np.frombuffer(out[1].cpu().numpy().tobytes(), dtype=RO.RESULT)[0]
-    msg_off, info, status, result = out
-    return (msg_off.cpu().numpy().view(np.uint64), info.cpu().numpy().reshape(-1).view(RO.INFO),
-            status.cpu().numpy().view(np.uint32), np.frombuffer(result.cpu().numpy().tobytes(), dtype=RO.RESULT)[0])
-
-
-def run_gpu(dev, region: bytes, start=0, max_m=64, shift=0, chain=False, workspace=None):
-    import torch
-
-    rw, r = place(region, shift)
-    out = (dev.chain_messages if chain else dev.recover_messages)(r, start, max_m, workspace=workspace)
-    torch.cuda.synchronize()
-    assert guards_intact(rw, shift, len(region)).tobytes() == region
-    return to_numpy(out)
-
-
-def assert_chain(got, offs, res, max_m):
-    msg_off, result = got
-    assert {k: int(result[k]) for k in RO.RESULT.names} == res
-    assert [int(x) for x in msg_off[:len(offs)]] == offs
-    assert len(msg_off) == max_m and all(int(x) == RO.NO_MESSAGE for x in msg_off[len(offs):])
-
-
 def same_as_cpu(got, cpu):
     assert np.array_equal(got[0], cpu[0]) and np.array_equal(got[2], cpu[2]) and got[3] == cpu[3]
     for name in RO.INFO.names:
@@ -57,11 +33,11 @@ def same_as_cpu(got, cpu):
 def check(dev, region, start=0, max_m=64, shift=0, oracle=True):
     """Chain and recover on the device against the CPU entry, and the oracle unless the region is large."""
     cpu = dev.recover_messages_cpu(region, start, max_m)
-    got = run_gpu(dev, region, start, max_m, shift)
+    got = run_recover(dev, region, start, max_m, shift)
     same_as_cpu(got, cpu)
     if oracle:
         RO.assert_call(got, RO.recover(region, start, max_m), max_m)
-        assert_chain(run_gpu(dev, region, start, max_m, shift, chain=True), *RO.chain_result(region, start, max_m),
+        assert_chain(run_recover(dev, region, start, max_m, shift, chain=True), *RO.chain_result(region, start, max_m),
                      max_m)
     return got
 
@@ -89,8 +65,6 @@ def exact_case(max_m):
     """Small messages of every stored format, one in twenty corrupted, ten more than max_m of them, and the
     oracle's recover and chain answers (this seed: no header among the first 410 is hit, so the chain fills
     every slot)."""
-    import rekey_oracle as RK
-
     region, _, _ = RK.build_region(n=max_m + 10, seed=1101, corrupt_frac=0.05, big_every=10**9, max_blob=600,
                                    max_usermeta=300)
     return region, RO.recover(region, 0, max_m), RO.chain_result(region, 0, max_m)
@@ -102,18 +76,17 @@ def test_exact_workspace_between_guards(dev, max_m):
     two guards, 0xA5 throughout: one slot, and the counts on either side of one plan block of the verify
     (5 jobs a message: 2,045 / 2,050 jobs), every slot filled. Both calls against the oracle and recover
     against the CPU entry; the workspaces' guards intact."""
-    from test_gpu_geometry import assert_guards, guarded_workspace
 
     region, exp, (coffs, cres) = exact_case(max_m)
     assert exp[3]["chained"] == cres["chained"] == max_m
     assert max_m == 1 or 10 <= sum(1 for s in exp[1] if s) <= max_m // 8  # refused and accepted messages both
     whole, ws = guarded_workspace(dev.recover_workspace_bytes(len(region), max_m))
-    got = run_gpu(dev, region, 0, max_m, shift=5, workspace=ws)
+    got = run_recover(dev, region, 0, max_m, shift=5, workspace=ws)
     assert_guards(whole, ws)
     same_as_cpu(got, dev.recover_messages_cpu(region, 0, max_m))
     RO.assert_call(got, exp, max_m)
     whole, ws = guarded_workspace(dev.chain_workspace_bytes(len(region), max_m))
-    got = run_gpu(dev, region, 0, max_m, shift=5, chain=True, workspace=ws)
+    got = run_recover(dev, region, 0, max_m, shift=5, chain=True, workspace=ws)
     assert_guards(whole, ws)
     assert_chain(got, coffs, cres, max_m)
 
@@ -170,7 +143,7 @@ def test_false_nodes(dev):
     for max_m in (1, 4, 8, 51):
         start, chained, calls = 0, [], 0
         while True:
-            msg_off, res = run_gpu(dev, region, start, max_m, chain=True)
+            msg_off, res = run_recover(dev, region, start, max_m, chain=True)
             chained += [int(x) for x in msg_off[:int(res["chained"])]]
             calls += 1
             assert all(int(x) == RO.NO_MESSAGE for x in msg_off[int(res["chained"]):])
@@ -192,10 +165,10 @@ def test_dense_false_nodes(dev):
         assert [int(x) for x in got[0][:300]] == inside and got[3]["end_status"] != 0
         got = check(dev, region, inside[150], 100, shift)  # max_m inside the dense blocks
         assert int(got[3]["chained"]) == 100 and got[3]["end_status"] != 0  # (no embedded header verifies)
-        _, res = run_gpu(dev, region, inside[150], 100, shift, chain=True)
+        _, res = run_recover(dev, region, inside[150], 100, shift, chain=True)
         assert int(res["chained"]) == 100 and res["more"] == 1 and int(res["end_off"]) == inside[250]
     for max_m in (3, 70, 299):
-        msg_off, res = run_gpu(dev, region, 0, max_m, chain=True)
+        msg_off, res = run_recover(dev, region, 0, max_m, chain=True)
         assert [int(x) for x in msg_off[:int(res["chained"])]] == offs[:int(res["chained"])]
         assert (res["more"] == 1) == (int(res["chained"]) < 4)
 
@@ -214,22 +187,22 @@ def test_doubling_rounds(dev, n):
     import torch
 
     region, one = RO.update_chain(n)
-    rw, r = place(region, 0)
+    rw, r = guarded(region, 0)
     want = np.arange(n, dtype=np.uint64) * np.uint64(one)
     pow2 = 1 << max(n - 1, 1).bit_length()
     for max_m in sorted({n, n - 1, pow2} - {0}):
-        msg_off, res = to_numpy(dev.chain_messages(r, 0, max_m))
+        msg_off, res = recover_to_numpy(dev.chain_messages(r, 0, max_m))
         k = min(n, max_m)
         assert int(res["chained"]) == k and np.array_equal(msg_off[:k], want[:k]), max_m
         assert (msg_off[k:] == np.uint64(RO.NO_MESSAGE)).all()
         if max_m < n:
             assert res["more"] == 1 and int(res["end_off"]) == k * one and res["end_status"] == 0
-            tail, res2 = to_numpy(dev.chain_messages(r, int(res["end_off"]), max_m))
+            tail, res2 = recover_to_numpy(dev.chain_messages(r, int(res["end_off"]), max_m))
             assert int(res2["chained"]) == 1 and int(tail[0]) == k * one  # the follow-up call completes it
             res = res2
         assert res["more"] == 0 and int(res["end_off"]) == len(region) and res["end_status"] == 0
     if n <= 4097:
-        got = to_numpy(dev.recover_messages(r, 0, n + 3))
+        got = recover_to_numpy(dev.recover_messages(r, 0, n + 3))
         same_as_cpu(got, dev.recover_messages_cpu(region, 0, n + 3))
         assert int(got[3]["recovered"]) == n
     torch.cuda.synchronize()
@@ -247,7 +220,7 @@ def test_stops(dev):
             assert all(got[1][i] == zero for i in range(9) if i >= n or got[2][i] != 0), name
     from ambry_amd import AmbryCrcError
 
-    _, r = place(b"\x00" * 64, 0)
+    _, r = guarded(b"\x00" * 64, 0)
     for start, max_m in ((65, 4), (0, 0), (0, 1 << 31)):
         for fn in (dev.chain_messages, dev.recover_messages):
             with pytest.raises(AmbryCrcError):
@@ -255,7 +228,7 @@ def test_stops(dev):
 
 
 def test_info_edge_cases(dev):
-    from test_recover_cpu import INFO_CASES
+    from recover_oracle import INFO_CASES
 
     key = MF.store_key
     msgs = [RO.put_message(key("p%d%d" % (sv, hv)), b"c" * (sv * 7), hv=hv, serde_version=sv, ttl=77 + sv,
@@ -283,7 +256,7 @@ def test_inert_slots(dev, mode):
     try:
         dev.set_region_mode(0, mode)
         for region, real in ((dirty, doffs), (clean, offs[:40])):
-            rw, r = place(region, 0)
+            rw, r = guarded(region, 0)
             want_st, want_end = dev.verify_messages(r, torch.tensor(real, dtype=torch.int64, device="cuda"))
             for mix in (real + [-1] * 300, real + [-1], [-1] * 5):
                 st, end = dev.verify_messages(r, torch.tensor(mix, dtype=torch.int64, device="cuda"))
@@ -292,7 +265,7 @@ def test_inert_slots(dev, mode):
                 assert torch.equal(st[:n], want_st[:n]) and torch.equal(end[:n], want_end[:n])
                 assert bool((st[n:] == MF.BAD_LAYOUT).all()) and bool((end[n:] == 0).all())
             guards_intact(rw, 0, len(region))
-            same_as_cpu(to_numpy(dev.recover_messages(r, 0, 700)), dev.recover_messages_cpu(region, 0, 700))
+            same_as_cpu(recover_to_numpy(dev.recover_messages(r, 0, 700)), dev.recover_messages_cpu(region, 0, 700))
     finally:
         dev.set_region_mode(0, before)
 
@@ -325,13 +298,13 @@ def test_chain_past_4gib(dev):
     want += [pos + o for o in soffs]
     assert want[3] > 1 << 32
     for start, first in ((0, 0), (want[2], 2), (want[50], 50)):
-        msg_off, res = to_numpy(dev.chain_messages(region, start, 128))
+        msg_off, res = recover_to_numpy(dev.chain_messages(region, start, 128))
         n = len(want) - first
         assert [int(x) for x in msg_off[:n]] == want[first:] and (msg_off[n:] == np.uint64(RO.NO_MESSAGE)).all()
         assert {k: int(res[k]) for k in RO.RESULT.names} == {"chained": n, "recovered": n, "end_off": total_len,
                                                             "end_status": 0, "more": 0}
     # the small messages alone, recovered at their offsets above 2^32
-    got = to_numpy(dev.recover_messages(region, want[3], 100))
+    got = recover_to_numpy(dev.recover_messages(region, want[3], 100))
     cpu = dev.recover_messages_cpu(small, 0, 100)
     assert np.array_equal(got[0], cpu[0] + np.uint64(want[3])) and np.array_equal(got[2], cpu[2])
     assert np.array_equal(got[1]["msg_off"], cpu[1]["msg_off"] + np.uint64(want[3]))
@@ -344,9 +317,6 @@ def test_above_the_capped_grids(dev):
     messages: every thread of the thread-per-message kernels takes a second message. The oracle judges one
     tile; offsets and infos of the copies are derived with numpy and compared on the device."""
     import torch
-
-    import rekey_oracle as RK
-    from test_gpu_scale import assert_guards, copies, dev as to_dev
 
     T = 1201
     tile, offs, _ = RK.build_region(n=T, seed=1, corrupt_frac=0.0, big_every=10**9, max_blob=1000, max_usermeta=400)
@@ -385,7 +355,7 @@ def test_recover_in_a_graph(dev):
     (clean, _, _), (dirty, _, _) = mixed()
     n = min(len(clean), len(dirty))
     a, b = clean[:n], dirty[:n]
-    rw, r = place(a, 0)
+    rw, r = guarded(a, 0)
     max_m = 400
     ws = torch.empty(dev.recover_workspace_bytes(n, max_m), dtype=torch.uint8, device="cuda")
     s = torch.cuda.Stream()
@@ -393,7 +363,7 @@ def test_recover_in_a_graph(dev):
     with torch.cuda.stream(s):
         out = dev.recover_messages(r, 0, max_m, workspace=ws)  # loads the kernels first
         torch.cuda.synchronize()
-        same_as_cpu(to_numpy(out), dev.recover_messages_cpu(a, 0, max_m))
+        same_as_cpu(recover_to_numpy(out), dev.recover_messages_cpu(a, 0, max_m))
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=s):
             dev.recover_messages(r, 0, max_m, workspace=ws, out=out)
@@ -405,5 +375,5 @@ def test_recover_in_a_graph(dev):
         torch.cuda.synchronize()
         g.replay()
         torch.cuda.synchronize()
-        same_as_cpu(to_numpy(out), dev.recover_messages_cpu(data, 0, max_m))
+        same_as_cpu(recover_to_numpy(out), dev.recover_messages_cpu(data, 0, max_m))
     assert dev.recover_messages_cpu(a, 0, max_m)[3] != dev.recover_messages_cpu(b, 0, max_m)[3]

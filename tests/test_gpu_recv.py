@@ -9,10 +9,11 @@ import numpy as np
 import pytest
 
 import recv_oracle as RO
+import rekey_oracle as RK
 import send_oracle as SO
 from datagen import stream_bytes
-from test_gpu_rekey import guards_intact, place
-from test_message_format import MF
+from gpu_buffers import assert_guards, guarded, guarded_workspace, guards_intact, u64_dev
+from msgfmt import MF
 
 pytestmark = pytest.mark.gpu
 
@@ -29,23 +30,17 @@ def messages(gpu):
     return M
 
 
-def _i64(values):
-    import torch
-
-    return torch.tensor(np.asarray(values, dtype=np.uint64).reshape(-1).view(np.int64), device="cuda")
-
-
 def run_gpu(messages, body: bytes, offs, sizes, flag, ranges=None, dst_off=None, shift=0, oshift=0, out_cap=64,
             workspace=None):
     """(status list, INFO array, the output view's bytes): guards checked around the body (which must be
     unchanged) and the output."""
     import torch
 
-    rw, r = place(body, shift)
-    ow, o = place(b"", oshift, out_cap)
-    _, info, status = messages.receive_blobs_dev(r, _i64(offs), flag, pay_size=None if sizes is None else _i64(sizes),
-                                                 ranges=None if ranges is None else _i64(ranges),
-                                                 dst_off=None if dst_off is None else _i64(dst_off), out=o,
+    rw, r = guarded(body, shift)
+    ow, o = guarded(b"", oshift, out_cap)
+    _, info, status = messages.receive_blobs_dev(r, u64_dev(offs), flag, pay_size=None if sizes is None else u64_dev(sizes),
+                                                 ranges=None if ranges is None else u64_dev(ranges),
+                                                 dst_off=None if dst_off is None else u64_dev(dst_off), out=o,
                                                  workspace=workspace)
     torch.cuda.synchronize()
     assert guards_intact(rw, shift, len(body)).tobytes() == body
@@ -165,8 +160,6 @@ def test_a_flipped_bit_in_any_piece_is_found(messages, n):
 def small_case(m, flag):
     """m payloads of small messages of every stored format (content <= 600 B), 10 % corrupted, sent under `flag`
     by the send oracle."""
-    import rekey_oracle as RK
-
     region, offs, _ = RK.build_region(n=m, seed=2000 + m, corrupt_frac=0.1 if m > 1 else 0.0, big_every=10**9,
                                       max_blob=600, max_usermeta=300)
     _, sinfo, body = SO.expected(region, offs, None, flag)
@@ -179,7 +172,6 @@ def small_case(m, flag):
 def test_exact_workspace_between_guards(messages, flag, m):
     """A caller workspace of exactly ambrycrc_receive_workspace_size(m) between two guards, 0xA5 throughout: one
     payload, and the counts on either side of one plan block of the placement scan (2,048 entries)."""
-    from test_gpu_geometry import assert_guards, guarded_workspace
 
     body, offs, sizes, exp = small_case(m, flag)
     if m > 1:
@@ -322,10 +314,10 @@ def test_graph_capture_and_replay(messages, flag):
     exp2 = RO.expected(body2, offs, sizes, flag, ranges=ranges, out_cap=len(exp[2]))
     assert exp2[0][victim] == MF.BLOB_CRC and exp2[0] != exp[0]
     cap = len(exp[2])
-    rw, r = place(body, 0)
-    ow, o = place(b"", 3, cap)
+    rw, r = guarded(body, 0)
+    ow, o = guarded(b"", 3, cap)
     fresh_o = ow.clone()
-    mo, ms, mr = _i64(offs), _i64(sizes), _i64(ranges)
+    mo, ms, mr = u64_dev(offs), u64_dev(sizes), u64_dev(ranges)
     ws = torch.empty(messages.receive_workspace_bytes(len(offs)), dtype=torch.uint8, device="cuda")
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
@@ -357,15 +349,13 @@ def test_send_then_receive_on_the_device(messages):
     converted on the host: every message the verify finds clean delivers exactly the oracle's blob content."""
     import torch
 
-    import rekey_oracle as RK
-
     region, offs, _ = RK.build_region(n=300, seed=4)
-    rw, r = place(region, 0)
-    sent, sinfo, sst = messages.send_messages_dev(r, _i64(offs), SO.BLOB)
+    rw, r = guarded(region, 0)
+    sent, sinfo, sst = messages.send_messages_dev(r, u64_dev(offs), SO.BLOB)
     torch.cuda.synchronize()
     si = sinfo.cpu().numpy().view(SO.INFO)
     body = sent[:max(int(si["send_len"].sum()), 1)]
-    out, info, status = messages.receive_blobs_dev(body, _i64(si["out_off"]), RO.BLOB, pay_size=_i64(si["send_len"]))
+    out, info, status = messages.receive_blobs_dev(body, u64_dev(si["out_off"]), RO.BLOB, pay_size=u64_dev(si["send_len"]))
     torch.cuda.synchronize()
     st, ri, host = status.cpu().numpy().view(np.uint32), info.cpu().numpy().view(RO.INFO), out.cpu().numpy()
     clean = 0

@@ -8,11 +8,12 @@ import pytest
 
 import rekey_oracle as RK
 from datagen import stream_bytes
-from test_message_format import MF
+from gpu_buffers import assert_guards, guarded, guarded_workspace, guards_intact
+from gpu_calls import assert_rekey_outputs, run_rekey
+from msgfmt import MF
+from regions import join, refused_messages
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 64
 
 
 @pytest.fixture(scope="module")
@@ -21,58 +22,6 @@ def messages(gpu):
 
     assert M.REKEY_DESC_DTYPE == RK.DESC
     return M
-
-
-def place(data: bytes, shift: int, size=None):
-    """(the whole tensor, the view of `size` bytes in it holding `data`): guards of 0xA5 around the view, which
-    starts `shift` bytes past a 64-B boundary of the allocation; bytes of the view past `data` are 0xA5 too."""
-    import torch
-
-    size = len(data) if size is None else size
-    buf = np.full(GUARD + shift + size + GUARD, 0xA5, dtype=np.uint8)
-    buf[GUARD + shift:GUARD + shift + len(data)] = np.frombuffer(data, dtype=np.uint8)
-    whole = torch.from_numpy(buf).cuda()
-    return whole, whole[GUARD + shift:GUARD + shift + size]
-
-
-def guards_intact(whole, shift: int, size: int) -> np.ndarray:
-    """The view's bytes, after checking the guards."""
-    h = whole.cpu().numpy()
-    assert (h[:GUARD + shift] == 0xA5).all() and (h[GUARD + shift + size:] == 0xA5).all(), "guard bytes overwritten"
-    return h[GUARD + shift:GUARD + shift + size]
-
-
-def run_gpu(messages, region: bytes, offs, descs, aux: bytes, shift=0, oshift=0, life=None, version=3, out_cap=None,
-            workspace=None):
-    """(status, out_off, out_len lists, the output view's bytes): guards checked around the region (which must
-    be unchanged), aux and the output."""
-    import torch
-
-    rw, r = place(region, shift)
-    aw, a = place(aux, 5)
-    cap = messages.rekey_out_bound(len(region), len(offs), len(aux)) if out_cap is None else out_cap
-    ow, o = place(b"", oshift, cap)
-    mo = torch.tensor(np.asarray(offs, dtype=np.uint64).view(np.int64), device="cuda")
-    dd = torch.from_numpy(np.ascontiguousarray(descs).view(np.uint8).reshape(-1).copy()).cuda()
-    lv = None if life is None else torch.tensor(np.asarray(life, dtype=np.int16), device="cuda")
-    _, out_off, out_len, status = messages.rekey_dev(r, mo, dd, a, header_version=version, life_version=lv, out=o,
-                                                     workspace=workspace)
-    torch.cuda.synchronize()
-    assert guards_intact(rw, shift, len(region)).tobytes() == region
-    assert guards_intact(aw, 5, len(aux)).tobytes() == aux
-    return (status.cpu().numpy().view(np.uint32).tolist(), out_off.cpu().numpy().view(np.uint64).tolist(),
-            out_len.cpu().numpy().view(np.uint64).tolist(), guards_intact(ow, oshift, cap))
-
-
-def assert_outputs(got, exp):
-    """Status, placement and every byte of every written span."""
-    st, off, ln, out = got
-    est, eoff, eln, packed = exp
-    assert st == est
-    assert off == eoff and ln == eln
-    for o, n in zip(eoff, eln):
-        if n:
-            assert out[o:o + n].tobytes() == packed[o:o + n], "message at output offset %d differs" % o
 
 
 @functools.lru_cache(maxsize=None)
@@ -90,8 +39,8 @@ def test_region_matches_oracle_and_cpu(messages, seed, shift, oshift):
     boundary and the output at two."""
     region, offs, descs, aux, exp = case(seed)
     RK.assert_mix(descs, exp[0])
-    got = run_gpu(messages, region, offs, descs, aux, shift, oshift)
-    assert_outputs(got, exp)
+    got = run_rekey(messages, region, offs, descs, aux, shift, oshift)
+    assert_rekey_outputs(got, exp)
     if shift == 0:
         cst, couts = RK.run_cpu(messages, region, offs, descs, aux)
         assert cst == got[0]
@@ -113,15 +62,14 @@ def test_exact_workspace_between_guards(messages, m):
     """A caller workspace of exactly ambrycrc_rekey_workspace_bytes(m) between two guards, 0xA5 throughout: one
     message, and the counts on either side of one plan block (4 copy jobs a message: 2,048 / 2,052 jobs).
     Status, placement and every output byte as the oracle's; the workspace's guards intact."""
-    from test_gpu_geometry import assert_guards, guarded_workspace
 
     region, offs, descs, aux, exp = exact_case(m)
     if m > 1:
         RK.assert_mix(descs, exp[0])
     whole, ws = guarded_workspace(messages.rekey_workspace_bytes(m))
-    got = run_gpu(messages, region, offs, descs, aux, shift=13, oshift=7, workspace=ws)
+    got = run_rekey(messages, region, offs, descs, aux, shift=13, oshift=7, workspace=ws)
     assert_guards(whole, ws)
-    assert_outputs(got, exp)
+    assert_rekey_outputs(got, exp)
 
 
 @pytest.mark.parametrize("version", [1, 2])
@@ -130,7 +78,7 @@ def test_header_versions_and_life(messages, version):
     life = [(7 * i) % 32768 for i in range(len(offs))]
     exp = RK.expected(region, offs, descs, aux, life=life, version=version)
     RK.assert_mix(descs, exp[0])
-    assert_outputs(run_gpu(messages, region, offs, descs, aux, shift=3, oshift=1, life=life, version=version), exp)
+    assert_rekey_outputs(run_rekey(messages, region, offs, descs, aux, shift=3, oshift=1, life=life, version=version), exp)
 
 
 def test_no_room_advances_the_running_offset(messages):
@@ -139,7 +87,7 @@ def test_no_room_advances_the_running_offset(messages):
     exp = RK.expected(region, offs, descs, aux, out_cap=cap)
     refused = sum(1 for s in exp[0] if s == RK.NO_ROOM)
     assert 50 <= refused and any(n for n in exp[2])
-    assert_outputs(run_gpu(messages, region, offs, descs, aux, shift=1, oshift=3, out_cap=cap), exp)
+    assert_rekey_outputs(run_rekey(messages, region, offs, descs, aux, shift=1, oshift=3, out_cap=cap), exp)
 
 
 def test_replacement_content_sizes(messages):
@@ -150,8 +98,8 @@ def test_replacement_content_sizes(messages):
     assert exp[0] == [0] * 7
     for version, oshift in ((3, 0), (1, 9)):
         exp = RK.expected(region, offs, descs, aux, version=version)
-        got = run_gpu(messages, region, offs, descs, aux, shift=2, oshift=oshift, version=version)
-        assert_outputs(got, exp)
+        got = run_rekey(messages, region, offs, descs, aux, shift=2, oshift=oshift, version=version)
+        assert_rekey_outputs(got, exp)
         for o, n in zip(got[1], got[2]):
             assert MF.verify_message(got[3][o:o + n].tobytes(), 0) == (0, n)
 
@@ -161,7 +109,7 @@ def test_single_message_and_one_past_a_block(messages):
     i = next(k for k, s in enumerate(exp[0]) if s == 0 and exp[2][k])
     one = RK.expected(region, [offs[i]], descs[i:i + 1], aux)
     assert one[0] == [0]
-    assert_outputs(run_gpu(messages, region, [offs[i]], descs[i:i + 1], aux, shift=9), one)
+    assert_rekey_outputs(run_rekey(messages, region, [offs[i]], descs[i:i + 1], aux, shift=9), one)
     # m = 257: small clean messages, one past a 256-thread block
     msgs = [RK.stored_put(MF.store_key("b%d" % k), MF.blob_properties_bytes(k, serde_version=1 + k % 5), b"u" * (k % 7),
                           stream_bytes(400 + k, 0, k).tobytes(), hv=1 + k % 3, bv=1 + k % 3) for k in range(257)]
@@ -169,19 +117,19 @@ def test_single_message_and_one_past_a_block(messages):
     descs2, aux2 = RK.build_descs(offs2, [False] * 257, seed=8, skip_frac=0.0, bad_frac=0.0)
     exp2 = RK.expected(b"".join(msgs), offs2, descs2, aux2)
     assert exp2[0] == [0] * 257
-    assert_outputs(run_gpu(messages, b"".join(msgs), offs2, descs2, aux2, shift=5, oshift=2), exp2)
+    assert_rekey_outputs(run_rekey(messages, b"".join(msgs), offs2, descs2, aux2, shift=5, oshift=2), exp2)
 
 
 def test_all_refused_and_all_skipped_write_nothing(messages):
     region, offs, descs, aux, exp = case(2)
     bad = [i for i, s in enumerate(exp[0]) if s != 0][:40]
     assert len({exp[0][i] for i in bad}) >= 4
-    st, off, ln, out = run_gpu(messages, region, [offs[i] for i in bad], descs[bad], aux, shift=1, oshift=1)
+    st, off, ln, out = run_rekey(messages, region, [offs[i] for i in bad], descs[bad], aux, shift=1, oshift=1)
     assert st == [exp[0][i] for i in bad] and ln == [0] * len(bad) and off == [RK.NOWHERE] * len(bad)
     assert (out == 0xA5).all()
     skip = descs[:50].copy()
     skip["key_len"] = 0
-    st, off, ln, out = run_gpu(messages, region, offs[:50], skip, aux, oshift=4)
+    st, off, ln, out = run_rekey(messages, region, offs[:50], skip, aux, oshift=4)
     assert st == [0] * 50 and ln == [0] * 50 and off == [RK.NOWHERE] * 50
     assert (out == 0xA5).all()
 
@@ -209,21 +157,19 @@ def test_runs_of_refused_messages(messages, run, where):
     inside the window after the one that reaches them, 64 can fill a window, 200 leave whole empty windows, so
     the jump is taken and must land on the first job after the run. At the start of the batch the search for the
     first share's job must skip the run; at the end the last slot's run starts at the total cost."""
-    from test_gpu_hard_delete import refused_messages
 
     puts = small_stored_puts()
     bad = refused_messages(run, "r%d" % run)
     first = {"start": 0, "middle": 150, "end": len(puts)}[where]
     msgs = puts[:first] + bad + puts[first:]
-    offs = [int(x) for x in np.cumsum([0] + [len(x) for x in msgs[:-1]])]
-    region = b"".join(msgs)
+    region, offs = join(msgs)
     descs, aux = RK.build_descs(offs, [False] * len(msgs), seed=9, skip_frac=0.0, bad_frac=0.0)
     exp = RK.expected(region, offs, descs, aux)
     est = exp[0]
     assert all(est[first:first + run]) and sum(1 for s in est if s) == run
     assert len(set(est[first:first + run])) == 3
-    got = run_gpu(messages, region, offs, descs, aux, shift=1, oshift=7)
-    assert_outputs(got, exp)
+    got = run_rekey(messages, region, offs, descs, aux, shift=1, oshift=7)
+    assert_rekey_outputs(got, exp)
     cst, couts = RK.run_cpu(messages, region, offs, descs, aux)
     assert cst == got[0]
     for b, o, n in zip(couts, got[1], got[2]):
@@ -236,10 +182,10 @@ def test_graph_capture_and_replay(messages):
     import torch
 
     region, offs, descs, aux, exp = case(1)
-    rw, r = place(region, 0)
-    aw, a = place(aux, 5)
+    rw, r = guarded(region, 0)
+    aw, a = guarded(aux, 5)
     cap = messages.rekey_out_bound(len(region), len(offs), len(aux))
-    ow, o = place(b"", 3, cap)
+    ow, o = guarded(b"", 3, cap)
     fresh_r, fresh_o = rw.clone(), ow.clone()
     mo = torch.tensor(np.asarray(offs, dtype=np.int64), device="cuda")
     dd = torch.from_numpy(np.ascontiguousarray(descs).view(np.uint8).reshape(-1).copy()).cuda()
@@ -251,7 +197,7 @@ def test_graph_capture_and_replay(messages):
         torch.cuda.synchronize()
         plain = (st0.cpu().numpy().view(np.uint32).tolist(), off0.cpu().numpy().view(np.uint64).tolist(),
                  len0.cpu().numpy().view(np.uint64).tolist(), guards_intact(ow, 3, cap).copy())
-        assert_outputs(plain, exp)
+        assert_rekey_outputs(plain, exp)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=s):
             _, off, ln, st = messages.rekey_dev(r, mo, dd, a, out=o, workspace=ws)
@@ -266,5 +212,5 @@ def test_graph_capture_and_replay(messages):
         torch.cuda.synchronize()
         got = (st.cpu().numpy().view(np.uint32).tolist(), off.cpu().numpy().view(np.uint64).tolist(),
                ln.cpu().numpy().view(np.uint64).tolist(), guards_intact(ow, 3, cap))
-        assert_outputs(got, exp)
+        assert_rekey_outputs(got, exp)
         assert got[:3] == plain[:3]

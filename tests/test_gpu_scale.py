@@ -25,68 +25,12 @@ import numpy as np
 import pytest
 
 import scale_tiles as S
+from gpu_buffers import assert_guards, dev, guarded, host
+from gpu_calls import assert_copies, assert_same, copies, offsets_dev
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
 T = S.T
-
-
-# ---------------------------------------------------------------- device helpers
-def dev(b):
-    """bytes or any numpy array -> a uint8 CUDA tensor of its bytes."""
-    import torch
-
-    if isinstance(b, (bytes, bytearray)):
-        a = np.frombuffer(b, dtype=np.uint8)
-    else:
-        a = np.ascontiguousarray(b).reshape(-1).view(np.uint8)
-    return torch.from_numpy(a.copy()).cuda()
-
-
-def guarded(n: int):
-    """(the whole tensor, its n-byte view between two guards), all 0xA5."""
-    import torch
-
-    whole = torch.full((GUARD + n + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    return whole, whole[GUARD:GUARD + n]
-
-
-def copies(tile_dev, k: int):
-    """(the whole tensor, the view) of k back-to-back copies of a device tile between guards."""
-    whole, view = guarded(k * tile_dev.numel())
-    view.copy_(tile_dev.repeat(k))
-    return whole, view
-
-
-def assert_guards(whole, n: int):
-    assert bool((whole[:GUARD] == 0xA5).all()) and bool((whole[GUARD + n:] == 0xA5).all()), "guard bytes overwritten"
-
-
-def assert_copies(view, tile_dev, k: int, what: str, starts=None):
-    """view is k copies of tile_dev, byte for byte; names the first copy, byte and tile message that differ."""
-    if tile_dev.numel() == 0 or k == 0:
-        return
-    ne = view.view(k, -1) != tile_dev
-    bad = ne.any(dim=1).cpu().numpy()
-    if bad.any():
-        c = int(np.nonzero(bad)[0][0])
-        b = int(ne[c].nonzero()[0])
-        msg = "" if starts is None else ", tile message %d" % (int(np.searchsorted(starts, b, side="right")) - 1)
-        raise AssertionError("%s: %d of %d copies differ; first copy %d, byte %d%s: %#x, expected %#x" % (
-            what, int(bad.sum()), k, c, b, msg, int(view.view(k, -1)[c, b]), int(tile_dev[b])))
-
-
-def host(t, dtype):
-    return t.cpu().numpy().reshape(-1).view(dtype)
-
-
-def assert_same(got, exp, what: str):
-    """Two numpy arrays, naming the first message that differs."""
-    if not np.array_equal(got, exp):
-        i = int(np.nonzero(got != exp)[0][0])
-        raise AssertionError("%s: %d of %d differ; first message %d (tile message %d): %s, expected %s" % (
-            what, int((got != exp).sum()), len(exp), i, i % T, got[i], exp[i]))
 
 
 # ---------------------------------------------------------------- the tile, on the host and on the device
@@ -109,12 +53,6 @@ def tile(gpu):
     t = S.tile()
     return SimpleNamespace(region_dev=dev(t.region), descs_dev=dev(t.descs), aux_dev=dev(t.aux),
                            life_dev=dev(t.life).view(torch.int16), **vars(t))
-
-
-def offsets_dev(offs, length: int, k: int):
-    import torch
-
-    return torch.from_numpy(S.tiled_offsets(offs, length, k)).cuda()
 
 
 @functools.lru_cache(maxsize=None)

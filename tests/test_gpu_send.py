@@ -10,8 +10,10 @@ import pytest
 import rekey_oracle as RK
 import send_oracle as SO
 from datagen import stream_bytes
-from test_gpu_rekey import guards_intact, place
-from test_message_format import MF
+from gpu_buffers import assert_guards, dev, guarded, guarded_workspace, guards_intact, host
+from gpu_calls import assert_copies, assert_same, assert_send_outputs, check_send, copies, offsets_dev, run_send
+from msgfmt import MF
+from regions import join
 
 pytestmark = pytest.mark.gpu
 
@@ -25,54 +27,6 @@ def messages(gpu):
 
     assert M.SEND_INFO_DTYPE == SO.INFO
     return M
-
-
-def run_gpu(messages, region: bytes, offs, sizes, flag, shift=0, oshift=0, out_cap=64, workspace=None):
-    """(status list, INFO array, the output view's bytes): guards checked around the region (which must be
-    unchanged) and the output."""
-    import torch
-
-    rw, r = place(region, shift)
-    ow, o = place(b"", oshift, out_cap)
-    mo = torch.tensor(np.asarray(offs, dtype=np.uint64).view(np.int64), device="cuda")
-    ms = None if sizes is None else torch.tensor(np.asarray(sizes, dtype=np.uint64).view(np.int64), device="cuda")
-    _, info, status = messages.send_messages_dev(r, mo, flag, msg_size=ms, out=o, workspace=workspace)
-    torch.cuda.synchronize()
-    assert guards_intact(rw, shift, len(region)).tobytes() == region
-    return (status.cpu().numpy().view(np.uint32).tolist(), info.cpu().numpy().view(SO.INFO),
-            guards_intact(ow, oshift, out_cap))
-
-
-def assert_outputs(got, exp):
-    """Status, every info field, every byte of every sent span, and 0xA5 everywhere else."""
-    st, info, out = got
-    est, einfo, packed = exp
-    assert st == list(est)
-    for name in SO.INFO.names:
-        if not np.array_equal(info[name], einfo[name]):
-            i = int(np.nonzero(info[name] != einfo[name])[0][0])
-            raise AssertionError("%s of message %d: %s, expected %s" % (name, i, info[name][i], einfo[name][i]))
-    untouched = np.ones(len(out), dtype=bool)
-    for f in einfo:
-        o, n = int(f["out_off"]), int(f["send_len"])
-        if n:
-            assert out[o:o + n].tobytes() == packed[o:o + n], "span at output offset %d differs" % o
-            untouched[o:o + n] = False
-    assert (out[untouched] == 0xA5).all(), "bytes written outside the sent spans"
-
-
-def check(messages, region, offs, sizes, flag, shift=0, oshift=0, out_cap=None, cpu=False, slack=0, workspace=None,
-          exp=None):
-    exp = SO.expected(region, offs, sizes, flag, out_cap=out_cap) if exp is None else exp
-    cap = max(len(exp[2]) + slack, 1) if out_cap is None else out_cap  # exactly the sum of the sent spans
-    got = run_gpu(messages, region, offs, sizes, flag, shift, oshift, cap, workspace)
-    assert_outputs(got, exp)
-    if cpu:
-        cst, cinfo, cout = SO.run_cpu(messages, region, offs, sizes, flag, out_cap=out_cap)
-        assert cst == got[0] and cout == exp[2]
-        for name in SO.INFO.names:
-            assert np.array_equal(cinfo[name], got[1][name]), name
-    return exp
 
 
 @functools.lru_cache(maxsize=None)
@@ -90,7 +44,7 @@ def test_region_matches_oracle_and_cpu(messages, flag, shift, oshift, sized):
     300 KB: one record across waves), the region at four offsets from a 64-B boundary and the output at two,
     with the header's sizes and with given ones; out_cap exactly the sum of the sent spans."""
     region, offs, sizes = region_case(1)
-    exp = check(messages, region, offs, sizes if sized else None, flag, shift, oshift, cpu=shift in (0, 1))
+    exp = check_send(messages, region, offs, sizes if sized else None, flag, shift, oshift, cpu=shift in (0, 1))
     clean, found, refused = SO.mix(exp[0], exp[1])
     assert clean >= 1 and found >= 1 and (refused >= 1 or (flag == SO.ALL and sized))
 
@@ -113,14 +67,13 @@ def test_exact_workspace_between_guards(messages, flag, m):
     message, and the counts on either side of one plan block of the per-message scans (2,048 entries). ALL
     with given sizes runs both scans (the placement and the plain copies), BLOB reads the encryption-key
     records first and refuses messages. Status, info and every output byte as the oracle's."""
-    from test_gpu_geometry import assert_guards, guarded_workspace
 
     region, offs, sizes, exp = exact_case(m, flag)
     clean, found, refused = SO.mix(exp[0], exp[1])
     if m > 1:
         assert clean >= 1000 and found >= 100 and (refused >= 20 or flag == SO.ALL)
     whole, ws = guarded_workspace(messages.send_workspace_bytes(m))
-    check(messages, region, offs, sizes, flag, shift=17, oshift=5, workspace=ws, exp=exp)
+    check_send(messages, region, offs, sizes, flag, shift=17, oshift=5, workspace=ws, exp=exp)
     assert_guards(whole, ws)
 
 
@@ -134,10 +87,6 @@ def sized_messages():
     return [MF.put_message(MF.store_key("size-%d" % n), MF.blob_properties_bytes(n), b"u" * (i % 9),
                            stream_bytes(900 + i, 0, n).tobytes(), version=3, enc_key=b"e" * 24 if i % 2 else None)
             for i, n in enumerate(SIZES)]
-
-
-def pack(msgs):
-    return b"".join(msgs), [int(x) for x in np.cumsum([0] + [len(b) for b in msgs[:-1]])]
 
 
 @pytest.mark.parametrize("flag", [SO.BLOB, SO.ALL, SO.BLOB_INFO], ids=FLAG_NAMES.get)
@@ -157,8 +106,8 @@ def test_blob_sizes_in_the_group_phase(messages, flag):
     big = sized_messages()
     msgs = small[:1000] + big[:8] + small[1000:2500] + big[8:] + small[2500:]
     assert len(msgs) >= 3277
-    region, offs = pack(msgs)
-    exp = check(messages, region, offs, None, flag, shift=3, oshift=5)
+    region, offs = join(msgs)
+    exp = check_send(messages, region, offs, None, flag, shift=3, oshift=5)
     assert sum(1 for s in exp[0] if s == 0) >= 3000
 
 
@@ -168,8 +117,8 @@ def test_blob_sizes_in_a_batch_of_7(messages, flag, part):
     """The same sizes seven at a time: every job through the sweep's wave mode."""
     msgs = sized_messages()[[0, 7, 9][part]:][:7]
     assert len(msgs) == 7
-    region, offs = pack(msgs)
-    exp = check(messages, region, offs, [len(b) for b in msgs] if part == 1 else None, flag, shift=part, oshift=5 * part)
+    region, offs = join(msgs)
+    exp = check_send(messages, region, offs, [len(b) for b in msgs] if part == 1 else None, flag, shift=part, oshift=5 * part)
     assert exp[0] == [0] * 7 and not exp[1]["check"].any()
 
 
@@ -178,7 +127,7 @@ def test_blob_sizes_in_a_batch_of_7(messages, flag, part):
 def test_each_rule(messages, flag, sized):
     """The fatal and the counted cases of test_send_cpu.py on the device, a size of 0 among them."""
     names, region, offs, sizes = SO.rule_cases()
-    exp = check(messages, region, offs, sizes if sized else None, flag, shift=1, oshift=2, cpu=not sized)
+    exp = check_send(messages, region, offs, sizes if sized else None, flag, shift=1, oshift=2, cpu=not sized)
     by = {n: i for i, n in enumerate(names)}
     if sized:
         assert exp[0][by["v3-size-0"]] == exp[0][by["past-region"]] == MF.BAD_LAYOUT
@@ -198,9 +147,9 @@ def test_blob_records_are_not_judged(messages, flag):
                            enc_key=b"k" * 20 if k % 2 else None)
         at = MF.parse_header(b, 0)[2][4] + 13 + k  # inside the content
         msgs.append(b[:at] + bytes([b[at] ^ 0x10]) + b[at + 1:])
-    region, offs = pack(msgs)
+    region, offs = join(msgs)
     assert all(MF.verify_message(region, o)[0] == MF.BLOB_CRC for o in offs)
-    exp = check(messages, region, offs, None, flag, shift=5)
+    exp = check_send(messages, region, offs, None, flag, shift=5)
     assert exp[0] == [0] * 40 and not exp[1]["check"].any()
 
 
@@ -216,7 +165,7 @@ def test_repeats_and_overlaps(messages, flag):
     at = MF.parse_header(outer, 0)[2][4] + 13 + 9
     assert region[at:at + len(inner)] == inner
     offs = [0, at, len(outer), 0, at, 0]
-    exp = check(messages, region, offs, None, flag, shift=7, oshift=1)
+    exp = check_send(messages, region, offs, None, flag, shift=7, oshift=1)
     assert exp[0] == [0] * 6 and not exp[1]["check"].any()
 
 
@@ -224,13 +173,13 @@ def test_single_message_and_one_past_a_block(messages):
     region, offs, sizes = region_case(1)
     for flag in SO.FLAGS:
         i = next(k for k, o in enumerate(offs) if SO.send_message(region, o, None, flag)[0] == 0)
-        check(messages, region, [offs[i]], None, flag, shift=9)
+        check_send(messages, region, [offs[i]], None, flag, shift=9)
     msgs = [RK.stored_put(MF.store_key("b%d" % k), MF.blob_properties_bytes(k, serde_version=1 + k % 5), b"u" * (k % 7),
                           stream_bytes(400 + k, 0, k).tobytes(), hv=1 + k % 3, bv=1 + k % 3,
                           enc_key=b"x" * (k % 30 + 1) if k % 4 == 0 else None) for k in range(257)]
-    region2, offs2 = pack(msgs)
+    region2, offs2 = join(msgs)
     for flag in (SO.BLOB, SO.BLOB_INFO, SO.ALL):
-        exp = check(messages, region2, offs2, None, flag, shift=5, oshift=2)
+        exp = check_send(messages, region2, offs2, None, flag, shift=5, oshift=2)
         assert exp[0] == [0] * 257
 
 
@@ -242,10 +191,10 @@ def test_every_message_refused_writes_nothing(messages, flag):
     else:
         bad, sizes = [o for o in offs if SO.send_message(region, o, None, flag)[0] != 0][:25], None
     assert len(bad) >= 5
-    st, info, out = run_gpu(messages, region, bad, sizes, flag, shift=1, oshift=1, out_cap=4096)
+    st, info, out = run_send(messages, region, bad, sizes, flag, shift=1, oshift=1, out_cap=4096)
     assert all(st) and (info["out_off"] == SO.NOWHERE).all() and not info["send_len"].any()
     assert (out == 0xA5).all()
-    assert_outputs((st, info, out), SO.expected(region, bad, sizes, flag))
+    assert_send_outputs((st, info, out), SO.expected(region, bad, sizes, flag))
 
 
 @pytest.mark.parametrize("flag", SO.FLAGS, ids=FLAG_NAMES.get)
@@ -257,7 +206,7 @@ def test_no_room_advances_the_running_offset(messages, flag):
     sent = [f for s, f in zip(full[0], full[1]) if s == 0]
     mid = sent[len(sent) // 2]
     cap = int(mid["out_off"]) + int(mid["send_len"]) // 2  # inside a message
-    exp = check(messages, region, offs, None, flag, shift=1, oshift=3, out_cap=cap, cpu=True)
+    exp = check_send(messages, region, offs, None, flag, shift=1, oshift=3, out_cap=cap, cpu=True)
     assert sum(1 for s in exp[0] if s == SO.NO_ROOM) >= 50 and len(exp[2]) <= cap
 
 
@@ -270,8 +219,8 @@ def test_graph_capture_and_replay(messages, flag):
     region, offs, _ = region_case(1)
     exp = SO.expected(region, offs, None, flag)
     cap = len(exp[2])
-    rw, r = place(region, 0)
-    ow, o = place(b"", 3, cap)
+    rw, r = guarded(region, 0)
+    ow, o = guarded(b"", 3, cap)
     fresh_r, fresh_o = rw.clone(), ow.clone()
     mo = torch.tensor(np.asarray(offs, dtype=np.int64), device="cuda")
     ws = torch.empty(messages.send_workspace_bytes(len(offs)), dtype=torch.uint8, device="cuda")
@@ -280,8 +229,8 @@ def test_graph_capture_and_replay(messages, flag):
     with torch.cuda.stream(s):
         _, info0, st0 = messages.send_messages_dev(r, mo, flag, out=o, workspace=ws)  # loads the kernels first
         torch.cuda.synchronize()
-        assert_outputs((st0.cpu().numpy().view(np.uint32).tolist(), info0.cpu().numpy().view(SO.INFO),
-                        guards_intact(ow, 3, cap).copy()), exp)
+        assert_send_outputs((st0.cpu().numpy().view(np.uint32).tolist(), info0.cpu().numpy().view(SO.INFO),
+                             guards_intact(ow, 3, cap).copy()), exp)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=s):
             _, info, st = messages.send_messages_dev(r, mo, flag, out=o, workspace=ws)
@@ -294,8 +243,8 @@ def test_graph_capture_and_replay(messages, flag):
         torch.cuda.synchronize()
         g.replay()
         torch.cuda.synchronize()
-        assert_outputs((st.cpu().numpy().view(np.uint32).tolist(), info.cpu().numpy().view(SO.INFO),
-                        guards_intact(ow, 3, cap)), exp)
+        assert_send_outputs((st.cpu().numpy().view(np.uint32).tolist(), info.cpu().numpy().view(SO.INFO),
+                             guards_intact(ow, 3, cap)), exp)
 
 
 @pytest.mark.parametrize("flag", [SO.BLOB, SO.BLOB_INFO], ids=FLAG_NAMES.get)
@@ -306,7 +255,6 @@ def test_send_above_the_caps(gpu, messages, flag):
     import torch
 
     import scale_tiles as S
-    from test_gpu_scale import assert_copies, assert_guards, assert_same, copies, dev, guarded, host, offsets_dev
 
     t = S.tile()
     k = S.copies_above_caps(torch.cuda.get_device_properties(0).multi_processor_count)

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import sweep_lattice as L
-from test_gpu_geometry import assert_guards, assert_untouched, guarded, guarded_workspace
+from gpu_buffers import assert_guards, assert_untouched, guarded, guarded_workspace
 
 pytestmark = pytest.mark.gpu
 

@@ -18,7 +18,7 @@ import pytest
 import ingest_oracle as IO
 import rekey_oracle as RK
 from datagen import stream_bytes
-from test_message_format import MF
+from msgfmt import MF
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BASELINE = os.environ.get("AMBRYCRC_ARGS_BASELINE") == "1"

@@ -8,7 +8,8 @@ import pytest
 
 import hard_delete_oracle as HD
 from datagen import stream_bytes
-from test_message_format import MF, build_region
+from msgfmt import MF
+from regions import join, verify_region
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -25,7 +26,7 @@ def device(ambry):
                 ids=lambda p: "seed%d-big%d" % p)
 def corrupt_case(request):
     seed, big = request.param
-    region, offs, _ = build_region(n=300, seed=seed, corrupt_frac=0.1, big_every=big)
+    region, offs, _ = verify_region(n=300, seed=seed, corrupt_frac=0.1, big_every=big)
     return region, offs, HD.hard_delete(region, offs)
 
 
@@ -51,7 +52,7 @@ def test_plan_only_writes_nothing(device, corrupt_case):
 def test_replay_with_recovery_info(device, seed):
     """HardDeleter's two phases: plan_only on the clean region gives the recovery info; a replay with it
     skips the record CRCs, so blobs corrupted in between are still deleted, with the expected bytes."""
-    region, offs, _ = build_region(n=300, seed=seed, corrupt_frac=0.0, big_every=17)
+    region, offs, _ = verify_region(n=300, seed=seed, corrupt_frac=0.0, big_every=17)
     est, einfo, eout = HD.hard_delete(region, offs)
     st, info, out = HD.run_cpu(device, region, offs, plan_only=True)
     assert st == est and np.array_equal(info, einfo) and out == region
@@ -67,7 +68,7 @@ def test_replay_with_recovery_info(device, seed):
 
 
 def test_bad_recovery_info_is_refused(device):
-    region, offs, _ = build_region(n=30, seed=4, corrupt_frac=0.0, big_every=10**9)
+    region, offs, _ = verify_region(n=30, seed=4, corrupt_frac=0.0, big_every=10**9)
     _, info, _ = HD.run_cpu(device, region, offs, plan_only=True)
     tried = 0
     for i, off in enumerate(offs):
@@ -106,9 +107,7 @@ def assembled_cases():
 
 def test_assembled_record_versions(device):
     cases = assembled_cases()
-    region = b"".join(m for _, m in cases)
-    offs = list(np.cumsum([0] + [len(m) for _, m in cases[:-1]]))
-    offs = [int(o) for o in offs]
+    region, offs = join([m for _, m in cases])
     est, einfo, eout = HD.hard_delete(region, offs)
     assert all(s == 0 for s in est)
     for (tag, _), inf in zip(cases, einfo):
@@ -128,7 +127,7 @@ def test_assembled_record_versions(device):
 
 
 def test_offsets_past_the_region_are_refused(device):
-    region, offs, _ = build_region(n=5, seed=9, corrupt_frac=0.0, big_every=10**9)
+    region, offs, _ = verify_region(n=5, seed=9, corrupt_frac=0.0, big_every=10**9)
     buf = np.frombuffer(region, dtype=np.uint8).copy()
     for off in (len(region), len(region) + 1, len(region) - 1, 2**63):
         st, inf = device.hard_delete_message_cpu(buf, off)
@@ -150,7 +149,7 @@ def test_hard_delete_cpu_under_asan(tmp_path):
 
     if not native_build.have_toolchain():
         pytest.skip("hipcc/g++ not available")
-    region, _, _ = build_region(n=24, seed=11, corrupt_frac=0.0, big_every=10**9)
+    region, _, _ = verify_region(n=24, seed=11, corrupt_frac=0.0, big_every=10**9)
     rf = tmp_path / "region.bin"
     rf.write_bytes(region)
     rf2 = tmp_path / "region2.bin"
@@ -158,6 +157,5 @@ def test_hard_delete_cpu_under_asan(tmp_path):
     exe = tmp_path / "hard_delete_asan"
     native_build.build_sanitized("hard_delete_asan.cpp", exe, tmp_path)
     for f in (rf, rf2):
-        r = subprocess.run([str(exe), str(f)], capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        assert "runs=" in r.stdout and "bad=0" in r.stdout
+        out = native_build.run_harness(exe, [f])
+        assert "runs=" in out and "bad=0" in out

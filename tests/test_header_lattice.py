@@ -10,7 +10,8 @@ import header_lattice as HL
 import recover_oracle as RO
 import rekey_oracle as RK
 import send_oracle as SO
-from test_message_format import MF
+from header_lattice import rekey_desc, sizes_of
+from msgfmt import MF
 
 
 @pytest.fixture(scope="module")
@@ -31,19 +32,6 @@ def messages(ambry):
 def verdicts():
     """{case name: the verify oracle's (status, end)}."""
     return {n: MF.verify_message(r, o) for n, r, o in HL.cases()}
-
-
-def sizes_of(region, offs):
-    """readSet.sizeInBytes for each message: the header's length where it parses, else up to the next offset."""
-    ends = list(offs[1:]) + [len(region)]
-    return [SO.header_length(region, o) or max(e - o, 0) for o, e in zip(offs, ends)]
-
-
-def rekey_desc():
-    d = np.zeros(1, dtype=RK.DESC)[0]
-    d["key_src"], d["key_len"], d["content_src"], d["props_blob_size"] = 1, 11, RK.KEEP, -1
-    d["account_id"], d["container_id"] = 77, -3
-    return d, b"." + b"new-key-xyz" + b"."
 
 
 def test_lattice_places_every_verdict():

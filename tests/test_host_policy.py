@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 
 from datagen import stream_bytes
-from test_message_format import MF, build_region
+from msgfmt import MF
+from regions import dense_v3_region, verify_region
 
 
 @pytest.fixture(scope="module")
@@ -47,7 +48,7 @@ def test_verify_messages_host_cpu_leg(ambry, seed):
     oracle's deserializeBlobAll reading, as the GPU leg's test_verify_messages_host_matches_oracle."""
     from ambry_amd import device as D
 
-    region, offs, expect = build_region(n=400, seed=seed, corrupt_frac=0.1)
+    region, offs, expect = verify_region(n=400, seed=seed, corrupt_frac=0.1)
     st, end = D.verify_messages_host(region, offs, device=-1)
     assert list(st) == [s for s, _ in expect]
     assert list(end) == [e for _, e in expect]
@@ -60,7 +61,7 @@ def test_transform_messages_host_cpu_leg(ambry):
     then a cap that holds only the first 20 outputs gives NO_ROOM after them, as the device batch."""
     from ambry_amd.messages import transform_host
 
-    region, offs, _ = build_region(n=300, seed=9, corrupt_frac=0.1)
+    region, offs, _ = verify_region(n=300, seed=9, corrupt_frac=0.1)
     life = np.random.default_rng(2).integers(0, 7, size=len(offs)).astype(np.int16)
     out, oo, ol, st = transform_host(region, offs, life_version=life, device=-1)
     pos = 0
@@ -95,11 +96,10 @@ def test_transform_messages_host_cpu_leg_fast_form(ambry):
     """The CPU leg over a dense region of canonical V3 PUTs (every message takes the fast form: its own
     bytes, life version and header CRC rewritten), with index life versions, against the oracle;
     then with no life versions, where the output is the region itself."""
-    from test_gpu_transform import dense_v3_region
 
     from ambry_amd.messages import transform_host
 
-    region, offs = dense_v3_region(MF, 300, seed=19)
+    region, offs = dense_v3_region(300, seed=19)
     life = np.random.default_rng(4).integers(0, 9, size=len(offs)).astype(np.int16)
     out, oo, ol, st = transform_host(region, offs, life_version=life, device=-1)
     assert list(st) == [0] * len(offs)

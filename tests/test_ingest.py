@@ -3,23 +3,19 @@ the oracle against the message-format oracle first, then status, every output by
 MessageInfo over mixed wire buffers, each refusal on its own, the refusal order, the growth bound, the pinned
 workspace size, and the wire parse and the workspace layout under ASan + UBSan as stand-alone programs."""
 import functools
-import json
-import os
 import shutil
 import struct
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
 import ingest_oracle as IO
-from test_message_format import MF
-from test_protocol import put_request_fields
-from test_workspace_layout import M_VALUES
+import native_build
+from msgfmt import MF
+from regions import put_request_fields
+from workspace_sizes import M_VALUES, recorded
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden", "ingest_workspace_size.json")
 SEEDS = [1, 2, 3]
 
 
@@ -218,24 +214,15 @@ def test_out_bound(messages):
 
 
 def test_workspace_size_is_pinned(messages):
-    with open(GOLDEN) as f:
-        want = json.load(f)
-    assert {str(m): messages.ingest_workspace_size(m) for m in M_VALUES} == want
+    assert {str(m): messages.ingest_workspace_size(m) for m in M_VALUES} == recorded("ingest_workspace_size")
 
 
-def _asan_program(tmp_path, name, extra=()):
+def _asan_program(tmp_path, name):
     if not shutil.which("g++"):
         pytest.skip("g++ not available")
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     exe = tmp_path / name
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", "-std=c++17", "-D__HIP_PLATFORM_AMD__",
-                    "-I" + os.path.join(rocm, "include"), "-I" + os.path.join(ROOT, "ambry_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "native", name + ".cpp"), *extra, "-o", str(exe)],
-                   check=True, timeout=300)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return r.stdout
+    native_build.build_host_sanitized(name + ".cpp", exe, flags=native_build.HIP_HEADERS)
+    return native_build.run_harness(exe, timeout=300)
 
 
 def test_wire_parse_under_asan(tmp_path):

@@ -11,6 +11,9 @@ import zlib
 import numpy as np
 import pytest
 
+from msgfmt import MF
+from regions import make_requests
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CORE = os.path.join(ROOT, "ambry_amd", "libambrycrc_jnicore.so")
 
@@ -230,7 +233,7 @@ def test_jni_shim_batched_transform(core, tmp_path):
     assert got["gpumsg_xform_room0"] == (0, "-") and got["gpumsg_xform_room1"] == (1 << 12, "-")
 
 
-def _sieve_response(mf):
+def _sieve_response():
     """One GetResponse as ReplicaThread hands it to MessageSievingInputStream: clean PUTs (header V1/V2/V3,
     some with an encryption key), one with a corrupt blob byte, one update record, and messages the
     index marks deleted or expired (read and skipped). Returns (bytes, [(size, flag, life)])."""
@@ -245,9 +248,9 @@ def _sieve_response(mf):
         v = 1 + i % 3
         enc = stream_bytes(i, 7, 32).tobytes() if v >= 2 and i % 4 == 1 else None
         if i == 17:
-            m = mf.update_message(mf.store_key("upd"), version=3)
+            m = MF.update_message(MF.store_key("upd"), version=3)
         else:
-            m = mf.put_message(mf.store_key("sv-%d" % i), mf.blob_properties_bytes(blen), b"m" * (i % 5),
+            m = MF.put_message(MF.store_key("sv-%d" % i), MF.blob_properties_bytes(blen), b"m" * (i % 5),
                                stream_bytes(300 + i, 0, blen).tobytes(), version=v, enc_key=enc, life=i % 3)
         if i == 23:
             m = bytearray(m)
@@ -267,12 +270,7 @@ def test_jni_sieve_call_sequence(core, tmp_path):
     ValidatingTransformer output (length and CRC), the corrupt one is skipped as invalid, and the
     update record is the exception that fails the stream -- the reference's outcomes, message by
     message."""
-    import importlib.util
-
-    spec = importlib.util.spec_from_file_location("message_format", os.path.join(ROOT, "oracle", "message_format.py"))
-    mf = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mf)
-    region, infos = _sieve_response(mf)
+    region, infos = _sieve_response()
     (tmp_path / "resp.bin").write_bytes(region)
     (tmp_path / "infos.txt").write_text("".join("%d %d %d\n" % x for x in infos))
     got = _run_harness(tmp_path, "sieve", str(tmp_path / "resp.bin"), str(tmp_path / "infos.txt"))
@@ -283,7 +281,7 @@ def test_jni_sieve_call_sequence(core, tmp_path):
         if flag:
             assert cls == (0, "-"), i
         else:
-            st, exp = mf.transform_message(region, at, life=life, version=3)
+            st, exp = MF.transform_message(region, at, life=life, version=3)
             if st == 0:
                 assert cls == (1, "-"), i
                 assert got["sieve_%d_len" % i] == (len(exp), "-"), i
@@ -296,16 +294,16 @@ def test_jni_sieve_call_sequence(core, tmp_path):
     assert seen == {1, 2, 3}
 
 
-def _log_span(mf, corrupt_at=None, truncate=False):
+def _log_span(corrupt_at=None, truncate=False):
     from datagen import stream_bytes
 
     msgs = []
     for i in range(30):
         if i % 6 == 4:
-            m = mf.update_message(mf.store_key("lg-%d" % i), version=1 + i % 3, life=i % 2)
+            m = MF.update_message(MF.store_key("lg-%d" % i), version=1 + i % 3, life=i % 2)
         else:
             blen = [0, 1, 700, 5000, 70000][i % 5]
-            m = mf.put_message(mf.store_key("lg-%d" % i), mf.blob_properties_bytes(blen), b"u" * (i % 7),
+            m = MF.put_message(MF.store_key("lg-%d" % i), MF.blob_properties_bytes(blen), b"u" * (i % 7),
                                stream_bytes(800 + i, 0, blen).tobytes(), version=1 + i % 3)
         msgs.append(m)
     if corrupt_at is not None:
@@ -318,12 +316,12 @@ def _log_span(mf, corrupt_at=None, truncate=False):
     return span, [len(m) for m in msgs]
 
 
-def _oracle_recover(mf, span):
+def _oracle_recover(span):
     """BlobStoreRecovery.recover's outcome (BlobStoreRecovery.java:43-110) by the oracle: messages from the
     span's start while each verifies, stopping at the first that does not (LogFileFormatError)."""
     pos, count = 0, 0
     while pos < len(span):
-        st, end = mf.verify_message(span, pos)
+        st, end = MF.verify_message(span, pos)
         if st or not end:
             return count, pos, 1
         count, pos = count + 1, end
@@ -338,15 +336,10 @@ def test_jni_recovery_call_sequence(core, tmp_path, case):
     the GPU, the first failure stopping the scan. Recovered count, reported startOffset and the
     LogFileFormatError equal the oracle's reading of the reference loop -- a clean span to its end, a
     corrupt blob byte in message 13, and a span whose last message is cut short."""
-    import importlib.util
-
-    spec = importlib.util.spec_from_file_location("message_format", os.path.join(ROOT, "oracle", "message_format.py"))
-    mf = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mf)
-    span, _ = _log_span(mf, corrupt_at=13 if case == "corrupt" else None, truncate=case == "truncated")
+    span, _ = _log_span(corrupt_at=13 if case == "corrupt" else None, truncate=case == "truncated")
     (tmp_path / "span.bin").write_bytes(span)
     got = _run_harness(tmp_path, "recover", str(tmp_path / "span.bin"), "7")
-    count, stop, failed = _oracle_recover(mf, span)
+    count, stop, failed = _oracle_recover(span)
     assert got["recover_init"] == (0, "-")
     assert (got["recover_count"][0], got["recover_stop"][0], got["recover_failed"][0]) == (count, stop, failed)
     assert failed == (case != "clean") and count == {"clean": 30, "corrupt": 13, "truncated": 29}[case]
@@ -442,7 +435,6 @@ def test_jni_put_crcs(core, tmp_path):
     record CRCs alone, and the argument errors (a wire output without fields, a short output, a negative blob
     length, a heap field buffer, a limit past the capacity) thrown."""
     from ambry_amd.protocol import blob_record_prefix_v3
-    from test_protocol import make_requests
 
     reqs = make_requests(n=12, seed=9)
     prefixes = [blob_record_prefix_v3(len(b), t, c) for _, b, c, t in reqs]

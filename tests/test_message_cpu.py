@@ -6,14 +6,15 @@ on corrupted regions, the record-level cases, every header version and life vers
 import numpy as np
 import pytest
 
-from test_message_format import MF, build_region, record_level_cases
+from msgfmt import MF
+from regions import dense_old_region, dense_v3_region, record_level_cases, replica_region, verify_region
 
 
 def test_verify_matches_oracle(ambry):
     from ambry_amd.messages import verify_message_cpu
 
     for seed in (1, 2, 3):
-        region, offs, expect = build_region(n=300, seed=seed, corrupt_frac=0.15)
+        region, offs, expect = verify_region(n=300, seed=seed, corrupt_frac=0.15)
         for o, e in zip(offs, expect):
             assert verify_message_cpu(region, o) == e, (seed, o)
     for msg, want in record_level_cases():
@@ -24,7 +25,7 @@ def test_verify_matches_oracle(ambry):
 def test_verify_truncated_and_out_of_range(ambry):
     from ambry_amd.messages import verify_message_cpu
 
-    region, offs, _ = build_region(n=40, seed=9, corrupt_frac=0.0)
+    region, offs, _ = verify_region(n=40, seed=9, corrupt_frac=0.0)
     cut = region[:offs[-1] + 57]  # the last message cut inside its records
     for o in offs:
         assert verify_message_cpu(cut, o) == MF.verify_message(cut, o), o
@@ -36,11 +37,9 @@ def test_verify_truncated_and_out_of_range(ambry):
 @pytest.mark.parametrize("version", [3, 2, 1])
 @pytest.mark.parametrize("life", [None, 5])
 def test_transform_matches_oracle(ambry, version, life):
-    from test_gpu_transform import build_region as transform_region
-
     from ambry_amd.messages import transform_message_cpu
 
-    region, offs = transform_region(MF, 300, seed=50 + version)
+    region, offs = replica_region(300, seed=50 + version)
     kinds = set()
     for o in offs:
         exp_st, exp = MF.transform_message(region, o, life=life, version=version)
@@ -56,11 +55,10 @@ def test_transform_fast_form_matches_oracle(ambry, life):
     """The CPU transform's fast form (V3 header, V3 blob record, properties already canonical
     VERSION_5 bytes: the message's own bytes with the life version and header CRC rewritten, as the
     GPU fast path does) against the oracle's full re-serialization, message by message."""
-    from test_gpu_transform import dense_v3_region
 
     from ambry_amd.messages import transform_message_cpu
 
-    region, offs = dense_v3_region(MF, 200, seed=61)
+    region, offs = dense_v3_region(200, seed=61)
     for o in offs:
         exp_st, exp = MF.transform_message(region, o, life=life, version=3)
         st, got = transform_message_cpu(region, o, header_version=3, life=life)
@@ -106,11 +104,10 @@ def test_transform_dense_old_region_bound(ambry):
     """Each old message (header V1/V2, SerDe V1-V3 properties, Blob_Format_V1) fits the ABI's
     bound for its own length (ambrycrc_transform_out_bound(len, 1)); the bound is tight for the
     worst case (V1 header + V1 props + blob V1 -> V3: exactly +26 B)."""
-    from test_gpu_transform import dense_old_region
 
     from ambry_amd.messages import TRANSFORM_GROWTH_MAX, out_bound, transform_message_cpu
 
-    region, offs = dense_old_region(MF, 200, seed=5)
+    region, offs = dense_old_region(200, seed=5)
     ends = offs[1:] + [len(region)]
     worst = 0
     for o, e in zip(offs, ends):
@@ -150,11 +147,10 @@ def test_transform_host_cpu_leg_writes_negative_life_versions(ambry):
     -1 (MessageInfo.LIFE_VERSION_FROM_FRONTEND) included, as ValidatingTransformer.java:90 writes
     msgInfo.getLifeVersion() and the device batch does: dense clean V3 messages (the CPU fast form) and
     the mixed region (the general form), against the oracle."""
-    from test_gpu_transform import build_region, dense_v3_region
 
     from ambry_amd.messages import transform_host
 
-    for region, offs in (dense_v3_region(MF, 60, seed=21), build_region(MF, 120, seed=22)):
+    for region, offs in (dense_v3_region(60, seed=21), replica_region(120, seed=22)):
         life = np.random.default_rng(8).integers(-2, 4, size=len(offs)).astype(np.int16)
         life[::5] = -1
         out, oo, ol, st = transform_host(region, offs, header_version=3, life_version=life, device=-1)

@@ -11,27 +11,8 @@ import numpy as np
 import pytest
 
 from datagen import stream_bytes
-from test_message_format import MF
-
-
-def put_request_fields(blob_id: bytes, props: bytes, um: bytes, blob_type: int, key: bytes, compressed: bool,
-                       blob_size: int) -> bytes:
-    return (blob_id + props + struct.pack(">i", len(um)) + um + struct.pack(">hh", blob_type, len(key)) + key +
-            struct.pack(">bq", 1 if compressed else 0, blob_size))
-
-
-def make_requests(n=20, seed=3):
-    rng = np.random.default_rng(seed)
-    reqs = []
-    for i in range(n):
-        size = int(rng.integers(0, 300000))
-        blob = stream_bytes(seed * 7919 + i, 0, size).tobytes()
-        key = stream_bytes(i, 1, 32 if i % 2 else 0).tobytes()
-        fields = put_request_fields(stream_bytes(i, 2, 40).tobytes(), MF.blob_properties_bytes(size),
-                                    stream_bytes(i, 3, int(rng.integers(0, 2000))).tobytes(), i % 3, key,
-                                    bool(i % 4 == 0), size)
-        reqs.append((fields, blob, bool(i % 4 == 0), i % 3))
-    return reqs
+from msgfmt import MF
+from regions import make_requests
 
 
 def test_put_crcs_one_pass_host(ambry):
@@ -110,28 +91,21 @@ def test_hard_delete_records_match_oracle(ambry):
     """HardDeleteMessageFormatInputStream.java:58-124: records rewritten with zero bytes and fresh
     CRCs; ambrycrc_zeros gives the same CRCs as scanning the zeros (oracle layouts + zlib), and a
     hard-deleted PUT message still verifies clean (oracle), as BlobStoreRecovery would see it."""
-    import importlib.util
-    import os
-
     from ambry_amd.protocol import hard_delete_records
 
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("mf", os.path.join(root, "oracle", "message_format.py"))
-    mf = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mf)
     for um_size, blob_size in ((0, 0), (1, 1), (1000, 65536), (7, 4 << 20), (4096, 1 << 20)):
         for ver in (2, 3):
             um, bl = hard_delete_records(um_size, blob_size, blob_version=ver)
-            assert um == mf.usermeta_record(bytes(um_size))
-            assert bl == mf.blob_record(bytes(blob_size), version=ver)
+            assert um == MF.usermeta_record(bytes(um_size))
+            assert bl == MF.blob_record(bytes(blob_size), version=ver)
             um2, bl2 = hard_delete_records(um_size, blob_size, blob_version=ver, zero_fill=False)
             assert um2[-8:] == um[-8:] and bl2[-8:] == bl[-8:]
     # a PUT message hard-deleted in place: same layout, zeroed user metadata and blob
-    key = mf.store_key("hd")
+    key = MF.store_key("hd")
     content = bytes(range(256)) * 300
-    msg = bytearray(mf.put_message(key, mf.blob_properties_bytes(len(content)), b"meta" * 50, content))
-    v, total, rel = mf.parse_header(bytes(msg), 0)
+    msg = bytearray(MF.put_message(key, MF.blob_properties_bytes(len(content)), b"meta" * 50, content))
+    v, total, rel = MF.parse_header(bytes(msg), 0)
     um, bl = hard_delete_records(200, len(content))
     msg[rel[3]:rel[3] + len(um)] = um
     msg[rel[4]:rel[4] + len(bl)] = bl
-    assert mf.verify_message(bytes(msg), 0) == (0, len(msg))
+    assert MF.verify_message(bytes(msg), 0) == (0, len(msg))

@@ -10,7 +10,7 @@ import pytest
 import geometry_lattice as G
 import kernel_model as KM
 import put_lattice as P
-from test_message_format import MF
+from msgfmt import MF
 
 
 @pytest.fixture(scope="module")

@@ -7,7 +7,9 @@ import numpy as np
 import pytest
 
 import recover_oracle as RO
-from test_message_format import MF
+from msgfmt import MF
+from oracle_common import LONG_MAX, wrap64
+from recover_oracle import INFO_CASES
 
 
 @pytest.fixture(scope="module")
@@ -86,15 +88,6 @@ def test_mixed_region_clean_and_corrupt(dev):
     assert stops >= 20 and covered >= 200, (stops, covered)
 
 
-INFO_CASES = [
-    ("ttl-forever", dict(ttl=-1), 0), ("creation-forever", dict(creation_ms=-1, ttl=50), 0),
-    ("ttl-negative", dict(ttl=-5), 0), ("ttl-saturates", dict(ttl=1 << 62), 0),
-    ("wraps", dict(creation_ms=(1 << 62) + 1, ttl=1 << 62), 0), ("creation-bad", dict(creation_ms=-2), RO.BAD_INFO),
-    ("ttl-min", dict(ttl=-(1 << 63)), 0), ("edge-over", dict(ttl=RO.LONG_MAX // 1000 + 1, creation_ms=5), 0),
-    ("edge-at", dict(ttl=RO.LONG_MAX // 1000, creation_ms=900), 0),
-]
-
-
 def test_info_edge_cases(dev):
     key = MF.store_key
     msgs, want = [], []
@@ -126,8 +119,8 @@ def test_info_edge_cases(dev):
     assert by["p23"]["life_version"] == 3 and by["p22"]["life_version"] == 0
     assert by["ttl-forever"]["expires_at_ms"] == -1 and by["creation-forever"]["expires_at_ms"] == -1
     assert by["ttl-negative"]["expires_at_ms"] == 1_700_000_000_000 - 5000
-    assert by["ttl-saturates"]["expires_at_ms"] == RO._wrap64(1_700_000_000_000 + RO.LONG_MAX) < 0
-    assert by["wraps"]["expires_at_ms"] == RO._wrap64((1 << 62) + 1 + RO.LONG_MAX) < 0
+    assert by["ttl-saturates"]["expires_at_ms"] == wrap64(1_700_000_000_000 + LONG_MAX) < 0
+    assert by["wraps"]["expires_at_ms"] == wrap64((1 << 62) + 1 + LONG_MAX) < 0
     assert by["never"]["flags"] == RO.DELETED and by["never"]["operation_time_ms"] == -1
     flags = sorted({(f["flags"], f["account_id"]) for f in infos if f["flags"]})
     assert flags == [(1, -3), (1, -1), (2, -3), (4, -3)]  # Update_Format_V1: a delete with -1, -1, -1
@@ -248,8 +241,6 @@ def test_recover_cpu_under_asan(tmp_path):
     """The CPU entry walks untrusted bytes: built with ASan + UBSan (host side) into a stand-alone program
     (tests/native/recover_asan.cpp) that runs it over every stop case, a corrupted region and the info edge
     cases, each as an exactly sized heap copy, from every message start and on every tail truncation."""
-    import subprocess
-
     import native_build
     import rekey_oracle as RK
 
@@ -264,6 +255,5 @@ def test_recover_cpu_under_asan(tmp_path):
         args.append(str(tmp_path / ("r%d.bin" % i)))
     exe = tmp_path / "recover_asan"
     native_build.build_sanitized("recover_asan.cpp", exe, tmp_path)
-    r = subprocess.run([str(exe)] + args, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "runs=" in r.stdout and "bad=0" in r.stdout
+    out = native_build.run_harness(exe, args)
+    assert "runs=" in out and "bad=0" in out

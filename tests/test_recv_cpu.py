@@ -2,22 +2,21 @@
 each rule of the entry once and which of two wins, status, info and every delivered byte over a region of every
 stored format sent under BLOB and ALL, with and without ranges, the struct's layout, the pinned workspace size,
 and recv.h -- the plan and the whole entry -- in a stand-alone program under ASan + UBSan."""
-import json
 import os
 import re
 import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import native_build
 import recv_oracle as RO
-from test_message_format import MF
+import rekey_oracle as RK
+from msgfmt import MF
+from workspace_sizes import M_VALUES, recorded
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden", "recv_workspace_size.json")
-M_VALUES = [1, 2, 409, 410, 512, 513, 1024, 1025, 2048, 2049, 65536, 1 << 20]
 FLAG_NAMES = {RO.BLOB: "blob", RO.ALL: "all"}
 
 
@@ -143,16 +142,12 @@ def test_invalid_arguments(messages):
 
 
 def test_workspace_size_is_pinned(messages):
-    with open(GOLDEN) as f:
-        want = json.load(f)
-    assert {str(m): messages.receive_workspace_bytes(m) for m in M_VALUES} == want
+    assert {str(m): messages.receive_workspace_bytes(m) for m in M_VALUES} == recorded("recv_workspace_size")
 
 
 def _asan_payloads(path):
     """Clean payloads for tests/native/recv_asan.cpp: [u32 flag][u32 length][bytes] each."""
     from datagen import stream_bytes
-
-    import rekey_oracle as RK
 
     items = []
     for bv in (1, 2, 3):
@@ -176,16 +171,11 @@ def asan_output(tmp_path_factory):
     if not shutil.which("g++"):
         pytest.skip("g++ not available")
     tmp = tmp_path_factory.mktemp("recv_asan")
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     exe = tmp / "recv_asan"
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", "-std=c++17", "-D__HIP_PLATFORM_AMD__",
-                    "-I" + os.path.join(rocm, "include"), "-I" + os.path.join(ROOT, "ambry_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "native", "recv_asan.cpp"), "-o", str(exe)], check=True, timeout=300)
+    native_build.build_host_sanitized("recv_asan.cpp", exe, flags=native_build.HIP_HEADERS)
     n = _asan_payloads(tmp / "payloads.bin")
-    r = subprocess.run([str(exe), str(tmp / "payloads.bin")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return n, r.stdout
+    out = native_build.run_harness(exe, [tmp / "payloads.bin"])
+    return n, out
 
 
 def test_plan_and_entry_under_asan(asan_output):

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import rekey_oracle as RK
-from test_message_format import MF
+from msgfmt import MF
 
 SEEDS = [1, 2, 3]
 
@@ -181,6 +181,5 @@ def test_rekey_cpu_under_asan(tmp_path):
         (tmp_path / name).write_bytes(data)
     exe = tmp_path / "rekey_asan"
     native_build.build_sanitized("rekey_asan.cpp", exe, tmp_path)
-    r = subprocess.run([str(exe)] + [str(tmp_path / n) for n in files], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "runs=" in r.stdout and "bad=0" in r.stdout
+    out = native_build.run_harness(exe, [str(tmp_path / n) for n in files])
+    assert "runs=" in out and "bad=0" in out

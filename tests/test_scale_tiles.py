@@ -6,7 +6,7 @@ import pytest
 
 import rekey_oracle as RK
 import scale_tiles as S
-from test_message_format import MF
+from msgfmt import MF
 
 
 @pytest.fixture(scope="module")

@@ -8,7 +8,8 @@ import pytest
 
 import rekey_oracle as RK
 import send_oracle as SO
-from test_message_format import MF
+from msgfmt import MF
+from oracle_common import same
 
 FLAG_NAMES = {SO.BLOB_PROPERTIES: "props", SO.BLOB_USER_METADATA: "usermeta", SO.BLOB: "blob", SO.ALL: "all",
               SO.BLOB_INFO: "info"}
@@ -42,8 +43,7 @@ def assert_same(got, exp):
     gst, ginfo, gout = got
     est, einfo, eout = exp
     assert list(gst) == list(est)
-    for name in SO.INFO.names:
-        assert np.array_equal(ginfo[name], einfo[name]), name
+    same(ginfo, einfo, "info")
     assert gout == eout
 
 
@@ -190,6 +190,5 @@ def test_send_cpu_under_asan(tmp_path):
         (tmp_path / name).write_bytes(data)
     exe = tmp_path / "send_asan"
     native_build.build_sanitized("send_asan.cpp", exe, tmp_path)
-    r = subprocess.run([str(exe)] + [str(tmp_path / n) for n in files], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "runs=" in r.stdout and "bad=0" in r.stdout
+    out = native_build.run_harness(exe, [str(tmp_path / n) for n in files])
+    assert "runs=" in out and "bad=0" in out

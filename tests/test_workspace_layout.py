@@ -3,17 +3,13 @@
 Every public *_workspace_bytes function is a workspace description run over null (csrc/ws_layout.h). Their
 values are part of the ABI -- a caller sizes its buffer by them -- so they are pinned to a recorded table;
 the descriptions themselves are walked by a stand-alone program under ASan + UBSan."""
-import json
-import os
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden", "workspace_bytes.json")
+import native_build
+from workspace_sizes import M_VALUES, recorded
 
-M_VALUES = [1, 2, 409, 410, 512, 513, 1024, 1025, 2048, 2049, 65536, 1 << 20]
 REGION_LENS = [0, 1, 4096, (1 << 20) + 1, 1 << 30]
 OF_M = ["ambrycrc_workspace_bytes", "ambrycrc_messages_workspace_bytes", "ambrycrc_serialize_puts_workspace_bytes",
         "ambrycrc_transform_workspace_bytes", "ambrycrc_rekey_workspace_bytes", "ambrycrc_send_workspace_bytes",
@@ -38,8 +34,7 @@ def test_every_size_function_is_recorded(ambry):
 
 def test_workspace_sizes_match_the_recorded_table(ambry):
     """Exactly the values recorded from the library before the sizes were derived from the descriptions."""
-    with open(GOLDEN) as f:
-        want = json.load(f)
+    want = recorded("workspace_bytes")
     got = size_table(ambry.lib())
     assert sorted(got) == sorted(want)
     for fn in want:
@@ -51,13 +46,7 @@ def test_layouts_under_asan(tmp_path):
     exactly that many malloc'd bytes and written end to end; arrays aligned, disjoint, inside the buffer."""
     if not shutil.which("g++"):
         pytest.skip("g++ not available")
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     exe = tmp_path / "ws_layout_asan"
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", "-std=c++17", "-D__HIP_PLATFORM_AMD__",
-                    "-I" + os.path.join(rocm, "include"), "-I" + os.path.join(ROOT, "ambry_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "native", "ws_layout_asan.cpp"), "-o", str(exe)],
-                   check=True, timeout=300)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "layouts=" in r.stdout and "bad=0" in r.stdout
+    native_build.build_host_sanitized("ws_layout_asan.cpp", exe, flags=native_build.HIP_HEADERS)
+    out = native_build.run_harness(exe, timeout=300)
+    assert "layouts=" in out and "bad=0" in out

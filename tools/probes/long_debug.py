@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Debug probe: one two-pass region verify of build_region(n, seed) (tests/test_message_format.py),
+"""Debug probe: one two-pass region verify of verify_region(n, seed) (tests/regions.py),
 status compared with the oracle; argv: n seed big_every."""
 import os
 import sys
@@ -14,10 +14,10 @@ def main():
     import torch
 
     from ambry_amd import device as D
-    from test_message_format import build_region
+    from regions import verify_region
 
     n, seed, big = int(sys.argv[1]), int(sys.argv[2]), int(float(sys.argv[3]))
-    region, offs, expect = build_region(n=n, seed=seed, corrupt_frac=0.08, big_every=big)
+    region, offs, expect = verify_region(n=n, seed=seed, corrupt_frac=0.08, big_every=big)
     torch.cuda.set_device(0)
     D.init(0)
     D.set_region_mode(0, 2)
