@@ -21,7 +21,8 @@ BAD_VERSION = MF.BAD_VERSION
 NOT_PUT = MF.NOT_PUT
 BAD_RECORD = MF.BAD_RECORD
 NOT_ENCODABLE = MF.NOT_ENCODABLE
-# every refusal a wire buffer can hold (NO_ROOM comes from out_cap; the Java-int refusal needs a 2 GiB frame)
+# every refusal a small wire buffer can hold (NO_ROOM comes from out_cap; the Java-int refusal needs a 2 GiB frame,
+# which test_gpu_big_blob.py builds on the device and big_message.frame_with_usermeta describes)
 WIRE_STATUSES = (BAD_DESC, NOT_PUT, BAD_VERSION, BAD_RECORD, WIRE_CRC, NOT_ENCODABLE, BAD_INFO)
 FIXED = 20      # size, type, version, correlationId, clientIdLen
 MIN_FRAME = 81  # FIXED + SerDe V1 with empty strings (39) + umSize + blobType + blobSize + CRC

@@ -143,6 +143,29 @@ def tiled_rekey_capped(status, out_len, k: int, out_cap: int):
             np.where(written, ln, 0))
 
 
+def tiled_recv_capped(status, info, k: int, out_cap: int):
+    """The packed receive of k copies of a tile's payloads into out_cap bytes, from recv_oracle.expected's
+    uncapped statuses and infos over one tile: a payload the rules accept (out_off set) takes the exclusive
+    running sum of the accepted lengths -- which advances past a payload without room too -- and is placed there
+    if it fits as recv_fits has it (at <= out_cap and len <= out_cap - at: an empty slice at out_cap fits, one past
+    it does not); otherwise it is refused with NO_ROOM, its info zero and out_off nowhere. A payload refused by
+    an earlier rule keeps its status and does not advance the sum. Returns (status, info, the end of the last
+    placed non-empty slice)."""
+    from oracle_common import NO_ROOM, NOWHERE as NOWHERE_U64
+
+    st, out = np.tile(np.asarray(status, dtype=np.uint32), k), np.tile(info, k)
+    accepted = out["out_off"] != np.uint64(NOWHERE_U64)
+    ln = np.where(accepted, out["out_len"], 0).astype(np.uint64)
+    pos = np.cumsum(ln, dtype=np.uint64) - ln
+    cap = np.uint64(out_cap)
+    fits = accepted & (pos <= cap) & (ln <= cap - np.minimum(pos, cap))
+    refused = accepted & ~fits
+    st[refused] = NO_ROOM
+    out[refused] = np.zeros((), dtype=out.dtype)
+    out["out_off"] = np.where(fits, pos, np.uint64(NOWHERE_U64))
+    return st, out, int((pos + ln)[fits & (ln > 0)].max(initial=0))
+
+
 def tiled_put_descs(descs, k: int, total: int, fields_len: int, blobs_len: int):
     """Serialize descriptors for k copies: out_off shifts by the tile's output bytes, the four field sources by
     the tile's field bytes, the blob source by its blob bytes (the source buffers are repeated too)."""

@@ -12,7 +12,8 @@ import recv_oracle as RO
 import rekey_oracle as RK
 import send_oracle as SO
 from datagen import stream_bytes
-from gpu_buffers import assert_guards, guarded, guarded_workspace, guards_intact, u64_dev
+from gpu_buffers import assert_guards, dev, guarded, guarded_workspace, guards_intact, host, u64_dev
+from gpu_calls import assert_same, copies
 from msgfmt import MF
 
 pytestmark = pytest.mark.gpu
@@ -153,6 +154,70 @@ def test_a_flipped_bit_in_any_piece_is_found(messages, n):
     body = b"".join(recs)
     exp = check(messages, body, offs, [len(rec)] * len(recs), RO.BLOB, ranges=[(lo, hi)] * len(recs), shift=5, oshift=2)
     assert exp[0] == [0] + [MF.BLOB_CRC] * len(places)
+
+
+ALL_LENS = (1, 2, 63, 64, 65, 200)
+
+
+@functools.lru_cache(maxsize=None)
+def range_case_all():
+    """Stored V3 PUTs with an encryption-key record (slot 3 filled) and without (slot 3 empty) for each content
+    length of ALL_LENS, as payloads under ALL: every (lo, hi), lo <= hi <= len, for the first five lengths, and
+    for 200 lo and hi from the edges of 64 either end, and to the end. 12,998 payloads, 77,988 jobs."""
+    msgs = [RK.stored_put(MF.store_key("range-%d-%d" % (n, e)), MF.blob_properties_bytes(n), b"um" * (n % 7),
+                          stream_bytes(600 + n, e, n).tobytes(), hv=3, enc_key=b"k" * 24 if e else None, bv=1 + k % 3)
+            for k, n in enumerate(ALL_LENS) for e in (0, 1)]
+    starts = [int(x) for x in np.cumsum([0] + [len(b) for b in msgs[:-1]])]
+    offs, sizes, ranges = [], [], []
+    for (n, e), at, b in zip([(n, e) for n in ALL_LENS for e in (0, 1)], starts, msgs):
+        if n <= 65:
+            pairs = [(lo, hi) for lo in range(n + 1) for hi in range(lo, n + 1)]
+        else:
+            pairs = [(lo, hi) for lo in _edges(n) for hi in _edges(n) if lo <= hi] + [(lo, RO.TO_END) for lo in _edges(n)]
+        for lo, hi in pairs:
+            offs.append(at)
+            sizes.append(len(b))
+            ranges.append((lo, hi))
+    body = b"".join(msgs)
+    return body, offs, sizes, ranges, RO.expected(body, offs, sizes, RO.ALL, ranges=ranges)
+
+
+def test_ranges_all(messages):
+    """test_ranges under ALL: the six-slot form, its slot 3 (the encryption-key record) filled and empty by
+    turns, the three content pieces at every cut of the short contents. Every 41st payload through the CPU
+    entry too."""
+    body, offs, sizes, ranges, exp = range_case_all()
+    assert len(offs) == 12998 and exp[0] == [0] * len(offs)
+    assert {int(x) != 0 for x in exp[1]["enckey_len"]} == {False, True}
+    check(messages, body, offs, sizes, RO.ALL, ranges=ranges, shift=3, oshift=1, exp=exp)
+    pick = slice(0, None, 41)
+    check(messages, body, offs[pick], sizes[pick], RO.ALL, ranges=ranges[pick], shift=5, oshift=2, cpu=True)
+
+
+@pytest.mark.parametrize("n", [5000, 70000])
+def test_a_flipped_bit_in_any_record_is_found(messages, n):
+    """A stored PUT with all four records under ALL with a range: one flipped bit in turn in the content, the
+    trailer's low word and its high word of the encryption-key, properties and user-metadata records, and in
+    each of the blob record's three content pieces -- each reports exactly its own record's bit, so slots 3-5
+    are each held to their own stored long. One in the header reports HEADER_CRC."""
+    put = RK.stored_put(MF.store_key("flip-%d" % n), MF.blob_properties_bytes(n), stream_bytes(78, 1, 300).tobytes(),
+                        stream_bytes(78, 2, n).tobytes(), hv=3, enc_key=stream_bytes(78, 3, 40).tobytes(), bv=3)
+    _, _, rel = MF.parse_header(put, 0)
+    lo, hi = 65, n - 65
+    places = []
+    for name, start, end, content, bit in (("enckey", rel[0], rel[1], rel[0] + 6 + 20, MF.ENCKEY_CRC),
+                                           ("props", rel[1], rel[3], rel[1] + 15, MF.PROPS_CRC),
+                                           ("usermeta", rel[3], rel[4], rel[3] + 6 + 150, MF.USERMETA_CRC)):
+        places += [(name + "-content", content, bit), (name + "-trailer-low", end - 1, bit),
+                   (name + "-trailer-high", end - 6, bit)]
+    c = rel[4] + 13
+    places += [("blob-before", c + 10, MF.BLOB_CRC), ("blob-inside", c + lo + 100, MF.BLOB_CRC),
+               ("blob-after", c + n - 3, MF.BLOB_CRC), ("header", 5, MF.HEADER_CRC)]
+    msgs = [put] + [RO._flip(put, at, 0x02) for _, at, _ in places]
+    offs = [i * len(put) for i in range(len(msgs))]
+    exp = check(messages, b"".join(msgs), offs, [len(put)] * len(msgs), RO.ALL, ranges=[(lo, hi)] * len(msgs), shift=5,
+                oshift=2)
+    assert exp[0] == [0] + [bit for _, _, bit in places], [name for (name, _, bit), s in zip(places, exp[0][1:]) if s != bit]
 
 
 # ---------------------------------------------------------------- 4. counts and workspace
@@ -343,7 +408,85 @@ def test_graph_capture_and_replay(messages, flag):
                            guards_intact(ow, 3, cap)), e)
 
 
-# ---------------------------------------------------------------- 7. send -> receive on the device
+# ---------------------------------------------------------------- 7. above the capped grids
+@functools.lru_cache(maxsize=None)
+def caps_tile(flag, layout):
+    """scale_tiles.tile() sent under `flag` by the send oracle, and recv_oracle.expected over that one tile for
+    the layout: (body, pay_off, pay_size, ranges or None, dst_off or None, the oracle's answers)."""
+    import scale_tiles as S
+
+    t = S.tile()
+    _, sinfo, body = SO.expected(t.region, [int(o) for o in t.offs], None, flag)
+    po, ps = [int(x) for x in sinfo["out_off"]], [int(x) for x in sinfo["send_len"]]
+    ranges = dst = None
+    if layout == "reversed-ranges":
+        ranges = RO.some_ranges(body, po, ps, flag)
+        free = RO.expected(body, po, ps, flag, ranges=ranges)
+        lens = [int(f["out_len"]) if int(f["out_off"]) != RO.NOWHERE else 0 for f in free[1]]
+        dst = [sum(lens) - sum(lens[:i + 1]) for i in range(len(lens))]
+        exp = RO.expected(body, po, ps, flag, ranges=ranges, dst_off=dst, out_cap=sum(lens))
+    else:
+        exp = RO.expected(body, po, ps, flag)
+    return body, po, ps, ranges, dst, exp
+
+
+@pytest.mark.parametrize("layout", ["packed", "reversed-ranges", "capped"])
+@pytest.mark.parametrize("flag", [RO.BLOB, RO.ALL], ids=FLAG_NAMES.get)
+def test_receive_above_the_caps(gpu, messages, flag, layout):
+    """The send oracle's body of tests/scale_tiles.py's tile, K times, at this device's m (more than twice the
+    capped grid of 4 blocks a CU): every thread of recv_plan_kernel, recv_place_kernel and recv_finish_kernel
+    takes a second and a third payload, a different tile message each trip, over slot-major arrays indexed
+    k * m + i. The oracle judges one tile; statuses and infos are tiled with numpy and the output is compared
+    on the device. packed: no ranges. reversed-ranges: a range for every payload and explicit destinations,
+    the whole batch in reverse payload order. capped: packed into half the need -- NO_ROOM from the first slice
+    that ends past the cap on, and no byte past the last placed slice changed."""
+    import torch
+
+    import scale_tiles as S
+
+    k = S.copies_above_caps(torch.cuda.get_device_properties(0).multi_processor_count)
+    body, po, ps, ranges, dst, (est, einfo, eout, loose) = caps_tile(flag, layout)
+    clean, crc, refused = RO.mix(est)
+    assert clean >= 100 and crc >= 10 and refused >= 100, (clean, crc, refused)
+    p, nb = len(eout), np.uint64(len(body))
+    copy = np.repeat(np.arange(k, dtype=np.uint64), S.T)
+    sent = np.tile(np.array(po, dtype=np.uint64) != np.uint64(RO.NOWHERE), k)
+    offs = np.where(sent, np.tile(np.array(po, dtype=np.uint64), k) + copy * nb, np.uint64(RO.NOWHERE))
+    placed = np.tile(einfo["out_off"] != np.uint64(RO.NOWHERE), k)
+    want_st, want_info, cap, end = np.tile(np.array(est, dtype=np.uint32), k), np.tile(einfo, k), k * p, k * p
+    dst_dev = None
+    if layout == "reversed-ranges":  # copy c lands at (k - 1 - c) * p
+        back = (np.uint64(k - 1) - copy) * np.uint64(p)
+        dst_dev = u64_dev(np.tile(np.array(dst, dtype=np.uint64), k) + back)
+        want_info["out_off"] = np.where(placed, np.tile(einfo["out_off"], k) + back, np.uint64(RO.NOWHERE))
+    elif layout == "capped":
+        cap = k * p // 2
+        want_st, want_info, end = S.tiled_recv_capped(est, einfo, k, cap)
+        assert (want_st == RO.NO_ROOM).sum() >= 100 * (k // 2) and cap - end < 4096
+    else:
+        want_info["out_off"] = np.where(placed, np.tile(einfo["out_off"], k) + copy * np.uint64(p), np.uint64(RO.NOWHERE))
+    tile_dev, out_tile, keep = dev(body), dev(eout), dev(~loose).bool()
+    whole, region = copies(tile_dev, k)
+    owhole, out = guarded(cap)
+    _, info, status = messages.receive_blobs_dev(region, u64_dev(offs), flag, pay_size=u64_dev(np.tile(ps, k)),
+                                                 ranges=None if ranges is None else u64_dev(np.tile(np.array(ranges, dtype=np.uint64), (k, 1))),
+                                                 dst_off=dst_dev, out=out)
+    torch.cuda.synchronize()
+    assert_same(host(status, np.uint32), want_st, "status")
+    got = host(info, np.uint8).view(RO.INFO)
+    for name in RO.INFO.names:
+        assert_same(got[name], want_info[name], name)
+    assert_guards(owhole, out.numel())
+    assert_guards(whole, region.numel())
+    full, part = end // p, end % p  # whole copies of the tile's output, then the placed part of one more
+    ne = (out[:full * p].view(full, p) != out_tile) & keep
+    assert not bool(ne.any()), "output: copy %d, byte %d differs" % tuple(int(x) for x in ne.nonzero()[0])
+    assert not bool(((out[full * p:end] != out_tile[:part]) & keep[:part]).any()), "the last, partial copy differs"
+    assert bool((out[end:] == 0xA5).all()), "bytes written past the last placed slice"
+    assert torch.equal(region.view(k, -1), tile_dev.expand(k, -1)), "the body changed"
+
+
+# ---------------------------------------------------------------- 8. send -> receive on the device
 def test_send_then_receive_on_the_device(messages):
     """ambrycrc_send_messages_dev(BLOB) over a stored region, its output fed to the receive with the info columns
     converted on the host: every message the verify finds clean delivers exactly the oracle's blob content."""

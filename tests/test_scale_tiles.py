@@ -135,3 +135,34 @@ def test_serialize(ambry, t, two):
     # the clean PUTs the descriptors came from verify clean again once serialized
     v, end = S.verify_oracle(out, np.cumsum(mlen) - mlen)
     assert (v == 0).all() and np.array_equal(end, np.cumsum(mlen))
+
+
+@pytest.mark.parametrize("flag_name", ["blob", "all"])
+def test_recv_out_cap(t, flag_name):
+    """The packed receive of three copies of the tile's sent body with out_cap inside the second copy: numpy's
+    running sum against recv_oracle.expected over the three copies -- statuses, every info field and the end of
+    the last placed slice. With room for everything it is the uncapped answer shifted copy by copy."""
+    import recv_oracle as RO
+    import send_oracle as SO
+
+    flag = {"blob": RO.BLOB, "all": RO.ALL}[flag_name]
+    _, sinfo, body = SO.expected(t.region, [int(o) for o in t.offs], None, flag)
+    po, ps = sinfo["out_off"].astype(np.uint64), sinfo["send_len"].astype(np.uint64)
+    st, info, out, _ = RO.expected(body, po, ps, flag)
+    p = len(out)
+    sent = np.tile(po != np.uint64(RO.NOWHERE), 3)
+    po3 = np.where(sent, np.tile(po, 3) + np.repeat(np.arange(3, dtype=np.uint64) * np.uint64(len(body)), S.T),
+                   np.uint64(RO.NOWHERE))
+    ps3 = np.tile(ps, 3)
+    for cap in (3 * p, p + p // 2, p + 1, p, p - 1, 0):
+        est, einfo, eend = S.tiled_recv_capped(st, info, 3, cap)
+        st3, info3, out3, _ = RO.expected(body * 3, po3, ps3, flag, out_cap=cap)
+        assert np.array_equal(np.array(st3, dtype=np.uint32), est), cap
+        for name in RO.INFO.names:
+            assert np.array_equal(info3[name], einfo[name]), (cap, name)
+        assert eend <= cap and (out3[eend:] == 0xA5).all()
+    est, einfo, eend = S.tiled_recv_capped(st, info, 3, p + p // 2)
+    assert p < eend <= p + p // 2
+    assert (est[:S.T] != RO.NO_ROOM).all() and (est[2 * S.T:] != 0).all()
+    refused = est[S.T:2 * S.T] == RO.NO_ROOM
+    assert refused.sum() >= 200 and (est[S.T:2 * S.T] == 0).sum() >= 200  # part of the second copy, not all of it
