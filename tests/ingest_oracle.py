@@ -164,72 +164,106 @@ REFUSALS = ("reserved", "off_past", "size_small", "size_big", "type", "version_l
             "flip_props", "flip_um", "flip_enc", "flip_blob", "crc_high", "non_ascii", "creation")
 
 
+# pairs of REFUSALS that write the same field of a frame, so one frame cannot hold both
+INCOMPATIBLE = {frozenset(p): why for p, why in (
+    (("version_low", "version_high"), "both set the request version"),
+    (("size_small", "size_big"), "both set the frame size"),
+    (("size_small", "no_crc"), "both set the frame size"),
+    (("size_big", "no_crc"), "both set the frame size"),
+    (("blob_neg", "blob_huge"), "both set the blob size"))}
+
+
 def one_frame(rng, i, seed, refusal=None, blob_len=None):
-    """(frame bytes, key_len, reserved, off_delta) of request i."""
+    """(frame bytes, key_len, reserved, off_delta) of request i. refusal: None, one of REFUSALS, or a tuple of
+    them that can coexist in one frame (INCOMPATIBLE lists the pairs that cannot)."""
+    rs = () if refusal is None else (refusal,) if isinstance(refusal, str) else tuple(refusal)
+    assert all(r in REFUSALS for r in rs) and not any(frozenset((a, b)) in INCOMPATIBLE for a in rs for b in rs)
     version = 3 + i % 3
     serde = 1 + (i // 3) % 5
     key_len = int(rng.choice([0, 24, 40, 57]))
     um_len = int(rng.choice([0, 1, 100, 777]))
     enc_len = int(rng.choice([0, 0, 32, 100])) if version >= 4 else 0
-    if refusal == "flip_enc":
+    if "flip_enc" in rs:
         version, enc_len = 4 + i % 2, 32
-    if refusal == "enc_neg":
+    if "enc_neg" in rs:
         version = 4 + i % 2
-    if refusal in ("flip_key", "key_over"):
+    if "flip_key" in rs or "key_over" in rs:
         key_len = 24
-    if refusal == "flip_um":
+    if "flip_um" in rs:
         um_len = 100
     if blob_len is None:
         blob_len = int(rng.choice([0, 1, 63, 300, 4096, 5000, 20000, 70001]))
-    if refusal == "flip_blob":
+    if "flip_blob" in rs:
         blob_len = max(blob_len, 1)
     client = b"" if i % 4 == 0 else b"client-%d" % i
     kw = dict(blob_type=i % 2, enc_key=nonzero_bytes(seed, 4 * i + 1, enc_len), compressed=int(rng.choice([0, 1, 2])),
               client_id=client, correlation=i, slack=int(rng.choice([0, 0, 0, 5])))
-    props = props_for(rng, blob_len, serde, non_ascii=refusal == "non_ascii",
-                      creation=-5 if refusal == "creation" else None)
+    props = props_for(rng, blob_len, serde, non_ascii="non_ascii" in rs,
+                      creation=-5 if "creation" in rs else None)
     reserved, ref_key = 0, key_len
-    if refusal == "reserved":
+    if "reserved" in rs:
         reserved = 1
-    elif refusal == "size_small":
+    if "size_small" in rs:
         kw["size"] = MIN_FRAME - 1
-    elif refusal == "size_big":
+    if "size_big" in rs:
         kw["size"] = 1 << 40
-    elif refusal == "type":
+    if "type" in rs:
         kw["type_"] = 2
-    elif refusal == "version_low":
+    if "version_low" in rs:
         kw["wire_version"] = 2
-    elif refusal == "version_high":
+    if "version_high" in rs:
         kw["wire_version"] = 6
-    elif refusal == "client_neg":
+    if "client_neg" in rs:
         kw["client_len"] = -1
-    elif refusal == "serde":
+    if "serde" in rs:
         props = struct.pack(">h", 9) + props[2:]
-    elif refusal == "um_neg":
+    if "um_neg" in rs:
         kw["um_size"] = -2
-    elif refusal == "blob_type":
+    if "blob_type" in rs:
         kw["blob_type"] = 2
-    elif refusal == "enc_neg":
+    if "enc_neg" in rs:
         kw["enc_len"] = -1
-    elif refusal == "blob_neg":
+    if "blob_neg" in rs:
         kw["blob_size"] = -1
-    elif refusal == "blob_huge":
+    if "blob_huge" in rs:
         kw["blob_size"] = INT_MAX + 1
-    elif refusal == "crc_high":
+    if "crc_high" in rs:
         kw["crc"] = None
     fr = frame(version, nonzero_bytes(seed, 4 * i, key_len), props, nonzero_bytes(seed, 4 * i + 2, um_len),
                nonzero_bytes(seed, 4 * i + 3, blob_len), **kw)
-    if refusal == "key_over":
+    if "key_over" in rs:
         ref_key = len(fr)
-    if refusal == "no_crc":  # the frame ends 4 bytes into its CRC
+    if "no_crc" in rs:  # the frame ends 4 bytes into its CRC
         fr = struct.pack(">q", len(fr) - kw["slack"] - 4) + fr[8:]
-    if refusal and refusal.startswith("flip_") or refusal == "crc_high":
+    for r in rs:
+        if not (r.startswith("flip_") or r == "crc_high"):
+            continue
         body = FIXED + len(client)
         at = {"flip_key": body, "flip_props": body + key_len + 5, "flip_um": body + key_len + len(props) + 4 + 7,
               "flip_enc": body + key_len + len(props) + 4 + um_len + 4 + 5,
-              "flip_blob": len(fr) - kw["slack"] - 8 - 1, "crc_high": len(fr) - kw["slack"] - 8 + 2}[refusal]
+              "flip_blob": len(fr) - kw["slack"] - 8 - 1, "crc_high": len(fr) - kw["slack"] - 8 + 2}[r]
         fr = fr[:at] + bytes([fr[at] ^ 0x10]) + fr[at + 1:]
-    return fr, ref_key, reserved, (1 << 50 if refusal == "off_past" else 0)
+    return fr, ref_key, reserved, (1 << 50 if "off_past" in rs else 0)
+
+
+def pair_wire(seed=5, clean_between=False):
+    """(wire, refs, pairs, skipped): one frame for every pair of REFUSALS that one frame can hold, in REFUSALS
+    order, small blobs, frames end to end; skipped: {pair: why} for the pairs left out (INCOMPATIBLE).
+    clean_between: a clean frame before each of them (None in pairs), so refused requests lie among placed ones."""
+    rng = np.random.default_rng(seed)
+    parts, refs, pairs, skipped, pos = [], [], [], {}, 0
+    for x, a in enumerate(REFUSALS):
+        for b in REFUSALS[x + 1:]:
+            if frozenset((a, b)) in INCOMPATIBLE:
+                skipped[a, b] = INCOMPATIBLE[frozenset((a, b))]
+                continue
+            for kind in ((None, (a, b)) if clean_between else ((a, b),)):
+                fr, key_len, reserved, delta = one_frame(rng, len(pairs), seed, kind, 40 + len(pairs) % 60)
+                parts.append(fr)
+                refs.append((pos + delta, key_len, reserved))
+                pairs.append(kind)
+                pos += len(fr)
+    return b"".join(parts), np.array(refs, dtype=REF), pairs, skipped
 
 
 def build_wire(n, seed, refused=0.1, gap=3, blobs=None):

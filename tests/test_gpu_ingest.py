@@ -56,6 +56,28 @@ def test_header_versions(messages, version):
     assert_ingest_outputs(run_ingest(messages, wire, refs, shift=3, oshift=1, version=version), exp)
 
 
+def test_two_refusal_causes_in_one_frame(messages):
+    """IO.pair_wire() as one batch (test_ingest.py says what it holds, test_refusal_order's pairs among them):
+    status, the wire CRC (0 where the parse refused), info, and nothing written for any of them. Then the same
+    frames between clean ones, so refused requests sit among placed messages: every output byte."""
+    wire, refs, pairs, _ = IO.pair_wire()
+    exp = IO.expected(wire, refs)
+    assert exp[0].all() and exp[6] == 0
+    got = run_ingest(messages, wire, refs, shift=5, oshift=3)
+    assert_ingest_outputs(got, exp)
+    assert (got[1] == IO.NOWHERE).all() and not got[2].any() and not got[4].view(np.uint8).any()
+    assert (got[6] == 0xA5).all()
+    buf = np.frombuffer(wire, dtype=np.uint8)
+    for i, r in enumerate(refs):
+        st, msg, crc, _ = messages.ingest_put_request_cpu(buf, int(r["off"]), int(r["key_len"]),
+                                                         reserved=int(r["reserved"]))
+        assert (st, crc, msg) == (got[0][i], got[3][i], None), pairs[i]
+    wire2, refs2, pairs2, _ = IO.pair_wire(clean_between=True)
+    exp2 = IO.expected(wire2, refs2)
+    assert all((p is None) == (st == 0) for p, st in zip(pairs2, exp2[0])) and len(pairs2) == 2 * len(pairs)
+    assert_ingest_outputs(run_ingest(messages, wire2, refs2, shift=1, oshift=7), exp2)
+
+
 # ---------------------------------------------------------------- the segment lattice
 LENS = (0, 1, 2, 3, 4, 5, 15, 16, 17, 63, 64, 65)
 BLOB_LENS = (255, 256, 257, 258, 4095, 4096, 4097, 4098, 16383, 16384, 16385, 16386, 65535, 65536, 65537, 131071,

@@ -185,6 +185,41 @@ def test_refusal_order(messages):
     assert run_cpu(messages, fr, 0, 24, out_cap=1)[0] == IO.NO_ROOM
 
 
+@functools.lru_cache(maxsize=None)
+def single_refusal_status():
+    """{cause: the oracle's status of a frame built with that cause alone}."""
+    out = {}
+    for a in IO.REFUSALS:
+        fr, key_len, reserved, delta = IO.one_frame(np.random.default_rng(1), 7, 5, a, 50)
+        out[a] = IO.ingest_request(fr, delta, key_len, 3, reserved)[0]
+    return out
+
+
+def test_two_refusal_causes_in_one_frame(messages):
+    """IO.pair_wire(): every pair of REFUSALS one frame can hold (the five left out write one field twice). The
+    oracle gives each frame the status of whichever of its two causes the reference reaches first (PutRequest
+    .readFrom's order: WIRE_STATUSES), so every wire status wins a pair -- but BAD_INFO: it is the last check and
+    has one cause (the creation time), so it loses all 23 of its pairs, which is asserted instead. The CPU entry
+    against the oracle: status, the wire CRC (0 where the parse refused), no message and no info."""
+    wire, refs, pairs, skipped = IO.pair_wire()
+    assert len(pairs) + len(skipped) == len(IO.REFUSALS) * (len(IO.REFUSALS) - 1) // 2 and len(skipped) == 5
+    single, order = single_refusal_status(), IO.WIRE_STATUSES.index
+    assert set(single.values()) == set(IO.WIRE_STATUSES)
+    buf = np.frombuffer(wire, dtype=np.uint8)
+    winners, parsed = set(), 0
+    for (a, b), r in zip(pairs, refs):
+        want = IO.ingest_request(wire, int(r["off"]), int(r["key_len"]), 3, int(r["reserved"]))
+        assert want[0] == min(single[a], single[b], key=order) and want[1] is None and want[3] is None, (a, b)
+        assert (want[2] != 0) == (want[0] in (IO.WIRE_CRC, IO.NOT_ENCODABLE, IO.BAD_INFO)), (a, b)
+        parsed += want[2] != 0
+        winners.add(want[0])
+        if "creation" in (a, b):
+            assert want[0] == single[a if b == "creation" else b] != IO.BAD_INFO, (a, b)
+        got = run_cpu(messages, buf, int(r["off"]), int(r["key_len"]), reserved=int(r["reserved"]))
+        assert got == want, (a, b)
+    assert winners == set(IO.WIRE_STATUSES) - {IO.BAD_INFO} and parsed >= 20
+
+
 def test_trailing_slack_is_tolerated(messages):
     for version in (3, 4, 5):
         fr, _ = clean_frame(version, slack=11)
